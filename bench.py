@@ -15,7 +15,15 @@ iterations in eager mode and as a captured hipGraph, bracketed by barrier + devi
 ranks; the faster mode is reported. `value` = ms per halo-exchange iteration (lower is better);
 `search_wall_s` is reported alongside.
 
+A plain run stops there: it writes its outputs if `--dump-outputs DIR` is given and prints the
+result line. `--full` adds everything else the record can carry, after the headline and within
+`--post-budget-s`: the timed schedule against the independent torch model, the per-link probes
+and the all-pairs link matrix (several ranks), the link model's check, the move's roof, the
+reference driver's layout and BASELINE configs 2 and 5 as searched, verified and timed
+sub-records.
+
   python bench.py --gpus 1 --steps 100 --warmup 20
+  python bench.py --gpus 1 --steps 100 --warmup 20 --full
   python -m torch.distributed.run --nproc-per-node 8 ... bench.py --gpus 8 --steps 100 --warmup 20
 """
 from __future__ import annotations
@@ -225,6 +233,127 @@ def link_probe(tz, halo, ctrl, iters, rccl=False):
             "busiest_link_at_probe_rate_ms": (busiest / (best * 1e9) * 1e3) if best else None}
 
 
+def shell_cells(k, n_zyx, g):
+    """(z, y, x) in the padded block of the k-th ghost cell (k: int64 tensor), counting the
+    ghost shell as: the 2g z-ghost planes, then the y-ghost rows of the other planes, then the
+    x-ghost cells of the other rows"""
+    import torch
+
+    nz, ny, nx = n_zyx
+    Y, X = ny + 2 * g, nx + 2 * g
+
+    def skip(i, n):  # ghost index 0..2g-1 along an axis -> its padded coordinate
+        return torch.where(i < g, i, i + n)
+
+    a, b = 2 * g * Y * X, nz * 2 * g * X
+    kb, kc = k - a, k - a - b
+    in_a, in_b = k < a, (k >= a) & (k < a + b)
+    z = torch.where(in_a, skip(k // (Y * X), nz),
+                    torch.where(in_b, g + kb // (2 * g * X), g + kc // (ny * 2 * g)))
+    y = torch.where(in_a, (k % (Y * X)) // X,
+                    torch.where(in_b, skip((kb % (2 * g * X)) // X, ny),
+                                g + (kc % (ny * 2 * g)) // (2 * g)))
+    x = torch.where(in_a, k % X, torch.where(in_b, kb % X, skip(kc % (2 * g), nx)))
+    return z, y, x
+
+
+_DUMP_SEED = 20261
+_DUMP_BYTES = {"ghosts": 48 << 20, "interior": 8 << 20}  # over all ranks: below 64 MB
+_DUMP_CHUNK = 1 << 25  # doubles of grid storage read at a time (256 MB)
+
+
+def dump_cells(name, n_zyx, g, cap, gen):
+    """(z, y, x) in the padded block of the cells the array `name` holds, and how many cells
+    there are to choose from: `ghosts` in `shell_cells` order, `interior` in ascending
+    (z, y, x) order; all of them, or `cap` of them drawn by `gen` (a seeded host generator:
+    the same cells for the same seed) and sorted: distinct ghost cells, interior cells with
+    repeats"""
+    import torch
+
+    nz, ny, nx = n_zyx
+    n_interior = nz * ny * nx
+    total = ((nz + 2 * g) * (ny + 2 * g) * (nx + 2 * g) - n_interior if name == "ghosts"
+             else n_interior)
+    if total <= cap:
+        k = torch.arange(total, dtype=torch.int64)
+    elif name == "ghosts":
+        k = torch.randperm(total, generator=gen)[:cap].sort().values
+    else:
+        k = torch.randint(total, (cap,), generator=gen, dtype=torch.int64).sort().values
+    if name == "ghosts":
+        return shell_cells(k, n_zyx, g) + (total,)
+    return g + k // (ny * nx), g + (k % (ny * nx)) // nx, g + k % nx, total
+
+
+def dump_file(name, rank, world):
+    return f"{name}.npy" if world == 1 else f"{name}_rank{rank}.npy"
+
+
+def read_storage(tz, halo, dev, flat):
+    """the grid storage's doubles at the indices `flat` (any shape, int64, host), read from the
+    grid in pieces of _DUMP_CHUNK doubles, so that no second copy of the grid is made"""
+    import torch
+
+    order = flat.reshape(-1).argsort()
+    want = flat.reshape(-1)[order]
+    got = torch.empty(want.numel(), dtype=torch.float64)
+    total = int(halo.grid_elems())
+    if want.numel() and not (0 <= int(want[0]) and int(want[-1]) < total):
+        raise ValueError("dump: a cell outside the grid storage")
+    buf = torch.empty(min(_DUMP_CHUNK, total), dtype=torch.float64, device=dev)
+    for c0 in range(0, total, _DUMP_CHUNK):
+        n = min(_DUMP_CHUNK, total - c0)
+        lo, hi = (int(v) for v in torch.searchsorted(want, torch.tensor([c0, c0 + n])))
+        if lo == hi:
+            continue
+        torch.cuda.synchronize(dev)
+        tz._tz.kernels.copy_bytes(buf.data_ptr(), halo.grid_ptr() + 8 * c0, 8 * n, 0)
+        torch.cuda.synchronize(dev)
+        got[lo:hi] = buf[(want[lo:hi] - c0).to(dev)].cpu()
+    out = torch.empty_like(got)
+    out[order] = got
+    return out.reshape(flat.shape)
+
+
+def dump_outputs(tz, halo, device, rank, world, path):
+    """--dump-outputs: this rank's grid as the last timed step left it, read through the
+    storage strides the workload reports: `ghosts` (nq, G) and `interior` (nq, I), the cells
+    `dump_cells` names, this rank's share of the size limit each. One rank writes <name>.npy,
+    several write <name>_rank<r>.npy. An error is recorded, not raised: the measurement is
+    complete by now and keeps its line (the run then exits with status 6)."""
+    import numpy as np
+    import torch
+
+    t0 = time.time()
+    info = {"dir": path, "seed": _DUMP_SEED, "arrays": {}}
+    try:
+        os.makedirs(path, exist_ok=True)
+        dev = torch.device(f"cuda:{device}")
+        layout = halo.layout()
+        g = int(layout["ghost"])
+        nq, Z, Y, X = (int(s) for s in layout["shape_qzyx"])
+        sq, sz, sy, sx = (int(s) for s in layout["strides_qzyx"])
+        base = int(layout["x_offset_cells"]) * sx
+        gen = torch.Generator().manual_seed(_DUMP_SEED)
+        for name in ("ghosts", "interior"):
+            cap = _DUMP_BYTES[name] // (8 * nq * world)
+            z, y, x, total = dump_cells(name, (Z - 2 * g, Y - 2 * g, X - 2 * g), g, cap, gen)
+            flat = (base + torch.arange(nq, dtype=torch.int64) * sq)[:, None] \
+                + (z * sz + y * sy + x * sx)[None, :]
+            vals = read_storage(tz, halo, dev, flat).numpy()
+            np.save(os.path.join(path, dump_file(name, rank, world)), vals)
+            info["arrays"][name] = {"shape": list(vals.shape), "of_cells": total,
+                                    "sampled": total > cap}
+        torch.cuda.empty_cache()
+    except Exception as e:  # noqa: BLE001 (the headline is final: it keeps its line)
+        info["error"] = f"{type(e).__name__}: {e}"
+        print(f"bench.py: rank {rank}: --dump-outputs failed: {info['error']}", file=sys.stderr,
+              flush=True)
+    info["s"] = round(time.time() - t0, 2)
+    return info
+
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -311,9 +440,20 @@ def main() -> int:
     ap.add_argument("--save-best", default="",
                     help="write the best schedule and this workload's options (rank 0) in the "
                          "format `python -m tenzing_amd run` and `tz-search --run` take")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run everything else the record can carry: "
+                         "the torch model check, the link probes, matrix and model check "
+                         "(several ranks), the move's roof and the sub-records (each still "
+                         "switched by its own option below). Off: the run ends with the headline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step left in this "
+                         "rank's grid as DIR/<name>.npy (float64): `ghosts`, the ghost cells the "
+                         "exchange filled, and `interior`, the cells it must leave alone; all "
+                         "of them, or a fixed seeded sample of a grid too large for 64 MB "
+                         "(the same cells in every run of the same arguments)")
     ap.add_argument("--link-probe-iters", type=int, default=20,
-                    help="several ranks: after the timing, measure what one xGMI link carries "
-                         "per transport (one face to one peer at a time; 0 = skip)")
+                    help="--full, several ranks: after the timing, measure what one xGMI link "
+                         "carries per transport (one face to one peer at a time; 0 = skip)")
     ap.add_argument("--link-probe-rccl", action="store_true",
                     help="also probe RCCL (off by default: an RCCL transfer has no device-side "
                          "timeout, and a hang there would cost the whole run's output)")
@@ -332,12 +472,12 @@ def main() -> int:
                          "rows sector-aligned, -1 = x=0 at the pitched row start (reference), "
                          "-2 = auto (16, line-aligned, in both orders)")
     ap.add_argument("--torch-model", default="on", choices=["on", "off"],
-                    help="after the headline: one more exchange of the timed schedule from a "
-                         "hashed field, checked against an independent torch model "
+                    help="--full, after the headline: one more exchange of the timed schedule "
+                         "from a hashed field, checked against an independent torch model "
                          "(`torch_model_check`)")
     ap.add_argument("--subrecords", default="auto", choices=["auto", "on", "off"],
-                    help="after the headline: BASELINE configs 2 (SpMV, band m / ranks) and 5 "
-                         "(SpMV + halo), each searched briefly over this run's transports, "
+                    help="--full, after the headline: BASELINE configs 2 (SpMV, band m / ranks) "
+                         "and 5 (SpMV + halo), each searched briefly over this run's transports, "
                          "verified and timed, and on one rank also the reference's XYZQ layout "
                          "and the move's roof (auto = on: every rank count; off: none)")
     ap.add_argument("--post-budget-s", type=float, default=150.0,
@@ -416,6 +556,7 @@ def main() -> int:
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": args.full,
         "ms_per_step": None,
         "higher_is_better": False,
         "scaling": "weak",
@@ -778,7 +919,16 @@ def main() -> int:
         "pad_streams": rt.pad_streams,
         "timed_graph_node_types": graph_nodes,
     })
-    # The headline is final. Everything after it is optional and bounded: from here the deadline
+    status = 0 if bad == 0 else 3
+    if args.dump_outputs:
+        # the grid as the last timed step left it (the final check above only read it); the
+        # deadline holds the complete line from here on
+        report()
+        out["dump_outputs"] = dump_outputs(tz, halo, device, rank, world, args.dump_outputs)
+        if ctrl.allreduce_max([1.0 if "error" in out["dump_outputs"] else 0.0])[0] > 0:
+            status = status or 6  # on every rank alike
+    # The headline is final, and a plain run ends here. Everything after it (--full) is
+    # optional and bounded: from here the deadline
     # prints this (complete) line and exits 0 if the sub-records or diagnostics do not finish
     # within --post-budget-s, so a stall there (e.g. the first cross-device transfer of a link
     # probe) cannot turn a finished measurement into a partial one.
@@ -819,10 +969,10 @@ def main() -> int:
     if deadline is not None:
         report()
         deadline.tighten(max(5.0, min(args.post_budget_s, deadline.remaining - 10.0)),
-                         0 if bad == 0 else 3)
+                         status)
 
     stuck = False
-    if args.torch_model == "on":
+    if args.full and args.torch_model == "on":
         # the timed schedule once more against a model that shares no code with the exchange
         # (tenzing_amd/utils/halo_ref.py): every rank loads its block of a hashed global field,
         # runs one exchange and compares its whole padded block with torch's periodic model
@@ -830,7 +980,7 @@ def main() -> int:
         post_done("torch_model", torch_model_check=_torch_model_check(tz, rt, ctrl, halo, device))
     # per-link bandwidth of each transport (context for the multi-GPU number: an exchange can
     # not beat the bytes its busiest link carries divided by what one link moves)
-    if world > 1 and args.link_probe_iters > 0:
+    if args.full and world > 1 and args.link_probe_iters > 0:
         post_phase("link_probe")
         probe = link_probe(tz, halo, ctrl, args.link_probe_iters, args.link_probe_rccl)
         post_done("link_probe", link_probe=probe)
@@ -853,7 +1003,7 @@ def main() -> int:
                                               "link_matrix": matrix})
             report(relay_shares={"offered": list(cfg.relay_fracs), "f_star_equal_rates": relay_share(),
                                  "f_star_link_matrix": round(f_meas, 3) if f_meas else None})
-    if rank == 0 and world > 1:
+    if args.full and rank == 0 and world > 1:
         post_phase("topology")
         from tenzing_amd.utils.env import xgmi_topology_summary
         post_done("topology", xgmi_topology=xgmi_topology_summary())
@@ -869,7 +1019,7 @@ def main() -> int:
                 val = {"error": f"{type(e).__name__}: {e}"}
             post_done("model_check", model_check=val)
 
-    subrecords = args.subrecords in ("on", "auto")
+    subrecords = args.full and args.subrecords in ("on", "auto")
     if subrecords and not stuck and world == 1 and halo.uses_direct():
         # the headline's move kernel against a kernel that touches exactly the same lines
         post_phase("move_roof")
@@ -907,8 +1057,8 @@ def main() -> int:
         # a diagnostic transfer never completed: the device may never drain, so the runtime's
         # teardown at exit could hang; the result is out, leave without it
         sys.stdout.flush()
-        os._exit(0 if bad == 0 else 3)
-    return 0 if bad == 0 else 3
+        os._exit(status)
+    return status
 
 
 def _torch_model_check(tz, rt, ctrl, halo, device):

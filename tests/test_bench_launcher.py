@@ -85,3 +85,69 @@ def test_launcher_world_from_each_launcher(monkeypatch):
     assert b.launched_world() == 3
     monkeypatch.setenv("WORLD_SIZE", "8")
     assert b.launched_world() == 8  # torchrun's variables win
+
+
+def _shell_order(n_zyx, g):
+    """the ghost cells in the order --dump-outputs documents, built from masks alone: the
+    z-ghost planes, then the y-ghost rows of the other planes, then the x-ghost cells of the
+    other rows, each part in ascending (z, y, x) order"""
+    import numpy as np
+
+    zg, yg, xg = np.meshgrid(*[(np.arange(n + 2 * g) < g) | (np.arange(n + 2 * g) >= n + g)
+                               for n in n_zyx], indexing="ij")
+    return np.concatenate([np.argwhere(zg), np.argwhere(~zg & yg), np.argwhere(~zg & ~yg & xg)])
+
+
+def test_dump_order_of_the_ghost_shell_covers_every_ghost_cell_once():
+    """--dump-outputs numbers the ghost cells of a padded block without building its mask: for
+    unequal extents the numbering gives the documented order exactly, and so reaches every
+    ghost cell of the independent model's mask once"""
+    import numpy as np
+    import torch
+
+    from tenzing_amd.utils.halo_ref import ghost_class
+
+    b = _bench_module()
+    for n_zyx, g in (((5, 4, 7), 2), ((3, 3, 3), 1), ((2, 6, 4), 3)):
+        total = int((ghost_class(n_zyx, g) > 0).sum())
+        got = torch.stack(b.shell_cells(torch.arange(total, dtype=torch.int64), n_zyx, g), dim=1)
+        want = _shell_order(n_zyx, g)
+        assert len(want) == total and np.array_equal(got.numpy(), want), (n_zyx, g)
+
+
+def test_dump_sample_is_seeded_and_stays_in_its_cell_class():
+    """a block too large for its share of the size limit: the sampled cells are the same for
+    the same seed, `cap` of them, sorted in the dump's order, ghosts distinct and all ghost
+    cells, interior cells all interior; a block that fits is dumped whole; several ranks write
+    one file per rank"""
+    import torch
+
+    b = _bench_module()
+    n_zyx, g = (9, 6, 11), 2
+    order = _shell_order(n_zyx, g)
+    where = {tuple(c): i for i, c in enumerate(order.tolist())}
+    picks = {}
+    for name in ("ghosts", "interior"):
+        for cap in (50, 10 ** 6):
+            runs = [b.dump_cells(name, n_zyx, g, cap, torch.Generator().manual_seed(7))
+                    for _ in range(2)]
+            assert all(torch.equal(u, v) for u, v in zip(runs[0][:3], runs[1][:3]))
+            z, y, x, total = runs[0]
+            cells = torch.stack([z, y, x], dim=1).tolist()
+            assert total == (len(order) if name == "ghosts" else 9 * 6 * 11)
+            assert len(cells) == min(cap, total)
+            if name == "ghosts":
+                pos = [where[tuple(c)] for c in cells]  # a KeyError: not a ghost cell
+                assert pos == sorted(set(pos))
+                if cap > total:
+                    assert pos == list(range(total))
+            else:
+                assert all(g <= c[k] < g + n_zyx[k] for c in cells for k in range(3))
+                assert cells == sorted(cells)
+                if cap > total:
+                    assert len(set(map(tuple, cells))) == total
+            picks[name, cap] = cells
+    other = b.dump_cells("ghosts", n_zyx, g, 50, torch.Generator().manual_seed(8))
+    assert torch.stack(other[:3], dim=1).tolist() != picks["ghosts", 50]
+    assert b.dump_file("ghosts", 0, 1) == "ghosts.npy"
+    assert b.dump_file("interior", 3, 8) == "interior_rank3.npy"

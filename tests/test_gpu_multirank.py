@@ -240,7 +240,8 @@ def test_bench_two_ranks_loopback(gpu, tmp_path, mode):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port),
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2",
-           "--cells", "64", "--mcts-iters", "6", "--bench-iters", "3", "--deadline-s", "240", "--subrecords", "off"]
+           "--cells", "64", "--mcts-iters", "6", "--bench-iters", "3", "--deadline-s", "240",
+           "--full", "--subrecords", "off"]
     env = dict(os.environ, TZ_IPC_GRID="1" if mode == "grid" else "0")
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=160, env=env)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
@@ -431,7 +432,7 @@ def test_bench_host_fallback_loopback(gpu, tmp_path):
            "--master-addr", "127.0.0.1", "--master-port", str(port),
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1",
            "--cells", "48", "--mcts-iters", "6", "--bench-iters", "2", "--deadline-s", "240", "--subrecords", "off",
-           "--link-probe-iters", "0", "--copy-puts", "off"]
+           "--link-probe-iters", "0", "--copy-puts", "off", "--dump-outputs", str(tmp_path / "dump")]
     env = dict(os.environ, TZ_FAIL_TRANSPORTS="ipc")
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=160, env=env)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
@@ -445,6 +446,23 @@ def test_bench_host_fallback_loopback(gpu, tmp_path):
     assert j["rccl_nranks"] is None
     # host ops cannot be captured: the candidates and the timing ran eagerly
     assert j["timed_mode"] == "eager"
+    # --dump-outputs on several ranks: one pair of files per rank; the ranks' interiors stacked
+    # along z (rank grid 1x1x2) and padded periodically give every rank's ghosts
+    import numpy as np
+
+    from test_bench_launcher import _shell_order
+
+    n, g, nq = 48, 3, 3
+    assert sorted(p.name for p in (tmp_path / "dump").iterdir()) == [
+        "ghosts_rank0.npy", "ghosts_rank1.npy", "interior_rank0.npy", "interior_rank1.npy"]
+    inner = [np.load(tmp_path / "dump" / f"interior_rank{r}.npy").reshape(nq, n, n, n) for r in (0, 1)]
+    want = np.pad(np.concatenate(inner, axis=1), ((0, 0), (g, g), (g, g), (g, g)), mode="wrap")
+    z, y, x = _shell_order((n, n, n), g).T
+    for r in (0, 1):
+        ghosts = np.load(tmp_path / "dump" / f"ghosts_rank{r}.npy")
+        assert ghosts.dtype == np.float64 and ghosts.shape == (nq, (n + 2 * g) ** 3 - n ** 3)
+        assert np.array_equal(ghosts, want[:, z + r * n, y, x]), r
+    assert len(np.unique(np.concatenate(inner))) == 2 * nq * n ** 3
 
 
 def test_copy_preflight_failure_drops_only_that_variant_loopback(gpu):
@@ -557,7 +575,7 @@ def test_bench_rccl_across_ranks_loopback(gpu):
            "--master-addr", "127.0.0.1", "--master-port", str(port),
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1",
            "--cells", "48", "--mcts-iters", "8", "--bench-iters", "2", "--deadline-s", "240", "--subrecords", "off",
-           "--link-probe-iters", "2", "--link-probe-rccl", "--hostsplit", "off"]
+           "--full", "--link-probe-iters", "2", "--link-probe-rccl", "--hostsplit", "off"]
     env = dict(os.environ, TZ_IPC_GRID="0", TZ_RCCL_LOOPBACK="1")
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=160, env=env)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
@@ -604,7 +622,7 @@ def test_bench_stall_after_headline_loopback(gpu, how):
            "--master-addr", "127.0.0.1", "--master-port", str(port),
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2",
            "--cells", "48", "--mcts-iters", "4", "--bench-iters", "3", "--deadline-s", "300",
-           "--link-probe-iters", "2", "--post-budget-s", "25", "--link-matrix-wait-s", "3"]
+           "--full", "--link-probe-iters", "2", "--post-budget-s", "25", "--link-matrix-wait-s", "3"]
     env = dict(os.environ)
     if how == "phase":
         env["TZ_BENCH_STALL"] = "link_matrix"
@@ -637,7 +655,7 @@ def test_bench_self_launched_two_ranks_with_subrecords_loopback(gpu):
                         "MASTER_PORT", "PMI_SIZE", "PMI_RANK", "PMIX_RANK")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20",
            "--warmup", "5", "--cells", "64", "--mcts-iters", "6", "--bench-iters", "3",
-           "--deadline-s", "280", "--link-probe-iters", "2"]
+           "--deadline-s", "280", "--full", "--link-probe-iters", "2"]
     r = subprocess.run(cmd, cwd="/tmp", capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     lines = [x for x in r.stdout.splitlines() if x.startswith("{")]
