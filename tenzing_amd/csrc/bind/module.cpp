@@ -532,6 +532,9 @@ PYBIND11_MODULE(_tz, m) {
       .def("__len__", &CsvBenchmarker::size);
   py::class_<ExecutorRunner>(m, "ExecutorRunner")
       .def("prepare", &ExecutorRunner::prepare, py::call_guard<py::gil_scoped_release>())
+      .def("prepare_many", &ExecutorRunner::prepare_many, py::arg("seqs"),
+           py::call_guard<py::gil_scoped_release>())
+      .def("select", &ExecutorRunner::select, py::arg("k"), py::call_guard<py::gil_scoped_release>())
       .def("run", &ExecutorRunner::run, py::call_guard<py::gil_scoped_release>());
   py::class_<HostExecutor, ExecutorRunner>(m, "HostExecutor", py::multiple_inheritance()).def(py::init<int>());
   py::class_<EmpiricalBenchmarker, Benchmarker>(m, "EmpiricalBenchmarker")

@@ -247,50 +247,21 @@ void HipRuntime::device_sync() {
   guarded(watchdogS_, "a device synchronization", [] { TZ_HIP(hipDeviceSynchronize()); });
 }
 
-void HipRuntime::destroy_exec(void *exec) {
-  if (!exec) return;
-  (void)hipGraphExecDestroy(static_cast<hipGraphExec_t>(exec));
-  auto it = graphOf_.find(exec);
-  if (it != graphOf_.end()) {
-    (void)hipGraphDestroy(static_cast<hipGraph_t>(it->second));
-    graphOf_.erase(it);
-  }
+void HipRuntime::drop_remainder() {
+  rem_.reset();
+  remR_ = 0;
 }
 
 void HipRuntime::destroy_graph() {
-  if (graphExecR_) { // always owned here, never by a slot
-    destroy_exec(graphExecR_);
-    graphExecR_ = nullptr;
-    remR_ = 0;
-  }
-  if (!slots_.empty()) {
-    // the current graphs are borrowed from a slot
-    for (Slot &s : slots_) {
-      destroy_exec(s.exec);
-      destroy_exec(s.execU);
-    }
-    slots_.clear();
-    graphExec_ = graphExecU_ = nullptr;
-    graphNodes_ = graphEdges_ = 0;
-    return;
-  }
-  if (graphExec_) {
-    destroy_exec(graphExec_);
-    graphExec_ = nullptr;
-    graphNodes_ = graphEdges_ = 0;
-  }
-  if (graphExecU_) {
-    destroy_exec(graphExecU_);
-    graphExecU_ = nullptr;
-  }
+  drop_remainder();
+  slots_.clear();
+  slot_ = 0;
 }
 
 std::map<std::string, int> HipRuntime::graph_node_types() const {
   std::map<std::string, int> out;
-  if (!graphExec_) return out;
-  auto it = graphOf_.find(graphExec_);
-  if (it == graphOf_.end()) return out;
-  hipGraph_t g = static_cast<hipGraph_t>(it->second);
+  if (!current().one) return out;
+  hipGraph_t g = static_cast<hipGraph_t>(current().one.source());
   size_t n = 0;
   TZ_HIP(hipGraphGetNodes(g, nullptr, &n));
   std::vector<hipGraphNode_t> nodes(n);
@@ -335,7 +306,7 @@ void HipRuntime::set_mode(ExecMode m) {
   }
 }
 
-void *HipRuntime::build_graph(int iterations, size_t &nodesOut, size_t &edgesOut) {
+CompiledGraph HipRuntime::build_graph(int iterations, size_t &nodesOut, size_t &edgesOut) {
   const int nS = num_streams();
   SyncModel model(nS);
   // per stream, in issue order: the graph nodes that stand for each issued GPU op. An op that
@@ -344,7 +315,7 @@ void *HipRuntime::build_graph(int iterations, size_t &nodesOut, size_t &edgesOut
   using NodeSet = std::vector<void *>;
   std::vector<std::vector<NodeSet>> nodes(nS);
   size_t edges = 0;
-  hipGraph_t graph = nullptr;
+  CompiledGraph cg;
   // a schedule with RCCL ops between ranks is built the way the RCCL preflight found exact
   bool rccl = false;
   for (const auto &e : seq_.entries)
@@ -397,32 +368,19 @@ void *HipRuntime::build_graph(int iterations, size_t &nodesOut, size_t &edgesOut
         }
         model.apply(op);
       }
-    graph = static_cast<hipGraph_t>(gb.finish());
+    cg = CompiledGraph::instantiate(gb.finish());
   }
-  try {
-    size_t real = 0;
-    TZ_HIP(hipGraphGetNodes(graph, nullptr, &real)); // the capture has ended: safe to inspect
-    hipGraphExec_t exec = nullptr;
-    TZ_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-    graphOf_[exec] = graph; // destroyed with the exec (destroy_exec)
-    graph = nullptr;
-    nodesOut = real;
-    edgesOut = edges;
-    TZ_LOG(Debug, "graph mode (" << capture_mode_name(mode) << " capture): " << iterations
-                                 << " iteration(s), " << real << " nodes, " << edges << " edges");
-    // upload once so the first timed launch does not pay for it
-    try {
-      TZ_HIP(hipGraphUpload(exec, S(streams_[0])));
-      TZ_HIP(hipStreamSynchronize(S(streams_[0])));
-    } catch (...) {
-      destroy_exec(exec);
-      throw;
-    }
-    return exec;
-  } catch (...) {
-    if (graph) (void)hipGraphDestroy(graph);
-    throw;
-  }
+  size_t real = 0;
+  // the capture has ended: safe to inspect
+  TZ_HIP(hipGraphGetNodes(static_cast<hipGraph_t>(cg.source()), nullptr, &real));
+  nodesOut = real;
+  edgesOut = edges;
+  TZ_LOG(Debug, "graph mode (" << capture_mode_name(mode) << " capture): " << iterations
+                               << " iteration(s), " << real << " nodes, " << edges << " edges");
+  // upload once so the first timed launch does not pay for it
+  cg.upload(streams_[0]);
+  TZ_HIP(hipStreamSynchronize(S(streams_[0])));
+  return cg;
 }
 
 namespace {
@@ -456,6 +414,29 @@ bool rccl_capture_settled() { return g_rcclCaptureSettled.load(); }
 
 const char *capture_mode_name(CaptureMode m) {
   return m == CaptureMode::Child ? "child" : "schedule";
+}
+
+CompiledGraph CompiledGraph::instantiate(void *graph) {
+  CompiledGraph cg;
+  cg.graph_ = graph; // owned from here on
+  hipGraphExec_t exec = nullptr;
+  TZ_HIP(hipGraphInstantiate(&exec, static_cast<hipGraph_t>(graph), nullptr, nullptr, 0));
+  cg.exec_ = exec;
+  return cg;
+}
+
+void CompiledGraph::launch(void *stream) const {
+  TZ_HIP(hipGraphLaunch(static_cast<hipGraphExec_t>(exec_), S(stream)));
+}
+
+void CompiledGraph::upload(void *stream) const {
+  TZ_HIP(hipGraphUpload(static_cast<hipGraphExec_t>(exec_), S(stream)));
+}
+
+void CompiledGraph::reset() {
+  if (exec_) (void)hipGraphExecDestroy(static_cast<hipGraphExec_t>(exec_));
+  if (graph_) (void)hipGraphDestroy(static_cast<hipGraph_t>(graph_));
+  exec_ = graph_ = nullptr;
 }
 
 GraphBuilder::GraphBuilder(const std::vector<void *> &streams, CaptureMode mode)
@@ -578,42 +559,36 @@ void HipRuntime::set_graph_unroll(int u) {
   }
 }
 
-void HipRuntime::prepare(const Sequence &seq) {
-  destroy_graph();
+HipRuntime::Slot HipRuntime::compile(const Sequence &seq) {
+  // also the schedule an eager run replays, should the compilation throw
   seq_ = seq;
   internalUsed_ = 0;
   expected_ = 0; // a new schedule: the watchdog floor alone bounds its first run
   event(std::max(0, seq.num_events() - 1)); // provision the event pool
+  Slot s;
+  s.seq = seq;
   if (mode_ == ExecMode::Graph && recordable(seq)) {
     size_t n = 0, e = 0;
-    graphExec_ = build_graph(1, graphNodes_, graphEdges_);
-    if (unroll_ > 1) graphExecU_ = build_graph(unroll_, n, e);
+    s.one = build_graph(1, s.nodes, s.edges);
+    if (unroll_ > 1) s.unrolled = build_graph(unroll_, n, e);
   }
+  return s;
+}
+
+void HipRuntime::prepare(const Sequence &seq) {
+  destroy_graph();
+  slots_.push_back(compile(seq));
+  select(0);
 }
 
 void HipRuntime::prepare_many(const std::vector<Sequence> &seqs) {
   destroy_graph();
-  std::vector<Slot> slots;
   try {
-    for (const Sequence &s : seqs) {
-      prepare(s); // compiles into graphExec_ / graphExecU_ (owned here until moved)
-      Slot sl;
-      sl.seq = s;
-      sl.exec = graphExec_;
-      sl.execU = graphExecU_;
-      sl.nodes = graphNodes_;
-      sl.edges = graphEdges_;
-      graphExec_ = graphExecU_ = nullptr;
-      slots.push_back(std::move(sl));
-    }
+    for (const Sequence &s : seqs) slots_.push_back(compile(s));
   } catch (...) {
-    for (Slot &s : slots) {
-      destroy_exec(s.exec);
-      destroy_exec(s.execU);
-    }
+    destroy_graph();
     throw;
   }
-  slots_ = std::move(slots);
   int events = 1;
   for (const Slot &s : slots_) events = std::max(events, s.seq.num_events());
   event(events - 1);
@@ -622,17 +597,9 @@ void HipRuntime::prepare_many(const std::vector<Sequence> &seqs) {
 
 void HipRuntime::select(size_t k) {
   TZ_CHECK(k < slots_.size(), "slot " << k << " out of range (" << slots_.size() << ")");
-  if (graphExecR_ && k != slot_) { // the remainder graph belongs to the previous slot's schedule
-    destroy_exec(graphExecR_);
-    graphExecR_ = nullptr;
-    remR_ = 0;
-  }
+  if (k != slot_) drop_remainder(); // it belongs to the previous slot's schedule
   const Slot &s = slots_[k];
   seq_ = s.seq;
-  graphExec_ = s.exec;
-  graphExecU_ = s.execU;
-  graphNodes_ = s.nodes;
-  graphEdges_ = s.edges;
   internalUsed_ = 0;
   slot_ = k;
   expected_ = s.expected;
@@ -801,35 +768,31 @@ void HipRuntime::run(int64_t n) {
   // what the next run of this schedule may take: its longest per-iteration time so far
   const double per = (wtime() - t0) / double(std::max<int64_t>(1, n));
   expected_ = std::max(expected_.load(), per);
-  if (!slots_.empty() && slot_ < slots_.size()) slots_[slot_].expected = expected_;
+  if (slot_ < slots_.size()) slots_[slot_].expected = expected_;
 }
 
 void HipRuntime::precompile(int64_t n) {
-  if (!graphExec_ || !graphExecU_ || unroll_ <= 1) return;
+  if (!current().one || !current().unrolled || unroll_ <= 1) return;
   const int64_t r = n % unroll_;
-  if (r <= 1 || (graphExecR_ && remR_ == r)) return;
-  if (graphExecR_) {
-    destroy_exec(graphExecR_);
-    graphExecR_ = nullptr;
-    remR_ = 0;
-  }
+  if (r <= 1 || (rem_ && remR_ == r)) return;
+  drop_remainder();
   size_t nodes = 0, edges = 0;
-  graphExecR_ = build_graph(int(r), nodes, edges);
+  rem_ = build_graph(int(r), nodes, edges);
   remR_ = r;
 }
 
 void HipRuntime::run_impl(int64_t n) {
-  if (graphExec_) {
-    hipStream_t origin = S(streams_[0]);
+  const Slot &cur = current();
+  if (cur.one) {
+    void *origin = streams_[0];
     int64_t i = 0;
-    if (graphExecU_)
-      for (; i + unroll_ <= n; i += unroll_)
-        TZ_HIP(hipGraphLaunch(static_cast<hipGraphExec_t>(graphExecU_), origin));
-    if (graphExecR_ && n - i == remR_) {
-      TZ_HIP(hipGraphLaunch(static_cast<hipGraphExec_t>(graphExecR_), origin));
+    if (cur.unrolled)
+      for (; i + unroll_ <= n; i += unroll_) cur.unrolled.launch(origin);
+    if (rem_ && n - i == remR_) {
+      rem_.launch(origin);
       i = n;
     }
-    for (; i < n; ++i) TZ_HIP(hipGraphLaunch(static_cast<hipGraphExec_t>(graphExec_), origin));
+    for (; i < n; ++i) cur.one.launch(origin);
     stream_sync(0);
   } else {
     const bool traced = trace_hooks().push != nullptr;

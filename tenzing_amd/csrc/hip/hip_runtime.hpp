@@ -34,7 +34,6 @@
 #include <memory>
 #include <string>
 #include <thread>
-#include <unordered_map>
 #include <vector>
 
 namespace tz {
@@ -52,6 +51,40 @@ struct HipRuntimeOpts {
   int graph_unroll = 1;        // iterations per hipGraph launch in Graph mode
   bool spin_sync = true;       // host syncs busy-poll (blocking waits measured no faster)
   int pad_streams = -1;        // streams owned at least (spares never used); -1: pad_streams()
+};
+
+/// One compiled hipGraph: a hipGraphExec_t together with the hipGraph_t it was instantiated from
+/// (both as void*). The only owner of either handle: the exec is destroyed first, then its
+/// source graph (not right after instantiation: some HIP releases keep referring to the source
+/// graph's nodes from the exec). Move-only; an empty one is false. The runtime's slots and
+/// remainder graph and the transports' preflights all hold their graphs through it.
+class CompiledGraph {
+public:
+  CompiledGraph() = default;
+  /// owns `graph` (a hipGraph_t) from the call on: destroyed here if instantiation throws
+  static CompiledGraph instantiate(void *graph);
+  ~CompiledGraph() { reset(); }
+  CompiledGraph(CompiledGraph &&o) noexcept : exec_(o.exec_), graph_(o.graph_) {
+    o.exec_ = o.graph_ = nullptr;
+  }
+  CompiledGraph &operator=(CompiledGraph &&o) noexcept {
+    if (this != &o) {
+      reset();
+      std::swap(exec_, o.exec_);
+      std::swap(graph_, o.graph_);
+    }
+    return *this;
+  }
+  explicit operator bool() const { return exec_ != nullptr; }
+  void launch(void *stream) const; // hipGraphLaunch
+  void upload(void *stream) const; // hipGraphUpload
+  /// the source hipGraph_t, for node inspection (nullptr when empty)
+  void *source() const { return graph_; }
+  /// destroy the exec, then the source graph (errors ignored); empty afterwards
+  void reset();
+
+private:
+  void *exec_ = nullptr, *graph_ = nullptr;
 };
 
 // ExecutorRunner first: the Python bindings expose HipRuntime through that base
@@ -86,7 +119,7 @@ public:
   /// run(n) bracketed by timing events on stream 0 (every op of a schedule follows the first
   /// event, and the schedule's closing host syncs precede the last): device seconds
   double run_device_timed(int64_t n) override;
-  int64_t batch_multiple() const override { return graphExecU_ ? unroll_ : 1; }
+  int64_t batch_multiple() const override { return current().unrolled ? unroll_ : 1; }
   /// graph mode with unroll u > 1: also compile a graph of the n % u iterations a run(n) leaves
   /// after its whole unrolled launches, so that run(n) launches ONE graph for them instead of
   /// n % u one-iteration graphs (each launch boundary of a multi-stream graph costs ~20 us;
@@ -101,13 +134,13 @@ public:
   ExecMode mode() const { return mode_; }
   /// mode actually used for the prepared sequence (Graph falls back to Eager when a host op
   /// cannot be recorded)
-  ExecMode effective_mode() const { return graphExec_ ? ExecMode::Graph : ExecMode::Eager; }
+  ExecMode effective_mode() const { return current().one ? ExecMode::Graph : ExecMode::Eager; }
   int device() const { return device_; }
   std::string device_name() const;
   /// number of top-level nodes of the compiled graph (0 in eager mode)
-  size_t graph_nodes() const { return graphNodes_; }
+  size_t graph_nodes() const { return current().nodes; }
   /// number of dependency edges of the compiled graph
-  size_t graph_edges() const { return graphEdges_; }
+  size_t graph_edges() const { return current().edges; }
   /// node count by type of the compiled single-iteration graph ("kernel", "host", "memcpy",
   /// "event_record", ...; empty in eager mode)
   std::map<std::string, int> graph_node_types() const;
@@ -145,11 +178,25 @@ public:
   std::vector<Span> trace(const Sequence &seq, int iterations = 1);
 
 private:
+  /// One prepared schedule. Slots own every compiled graph; "current" is an index into them.
+  struct Slot {
+    Sequence seq;
+    CompiledGraph unrolled, one; // unroll_ iterations, one iteration (destroyed in reverse)
+    size_t nodes = 0, edges = 0;
+    double expected = 0;
+  };
+  /// the selected slot (an empty one: nothing prepared, or dropped by set_mode / set_graph_unroll)
+  const Slot &current() const {
+    static const Slot none;
+    return slot_ < slots_.size() ? slots_[slot_] : none;
+  }
   void *event(int e);
   void *internal_event();
   void destroy_graph();
+  void drop_remainder();
   bool recordable(const Sequence &seq) const;
-  void *build_graph(int iterations, size_t &nodes, size_t &edges);
+  Slot compile(const Sequence &seq);
+  CompiledGraph build_graph(int iterations, size_t &nodes, size_t &edges);
   void run_impl(int64_t n);
   /// run `body` (a blocking wait on the device) under the watchdog with `budget` seconds
   void guarded(double budget, const char *what, const std::function<void()> &body);
@@ -166,25 +213,12 @@ private:
   void *timerEv_[2] = {nullptr, nullptr};
   size_t internalUsed_ = 0;
   Sequence seq_;
-  void *graphExec_ = nullptr;  // one iteration
-  void *graphExecU_ = nullptr; // unroll_ iterations
-  void *graphExecR_ = nullptr; // remR_ iterations (precompile)
+  std::vector<Slot> slots_; // prepare: one; prepare_many: one per sequence
+  size_t slot_ = 0;         // selected slot (select)
+  CompiledGraph rem_;       // remR_ iterations of the selected slot's schedule (precompile)
   int64_t remR_ = 0;
-  // the source graph of every instantiated exec, destroyed together with it (not right after
-  // instantiation: some HIP releases keep referring to the source graph's nodes from the exec)
-  std::unordered_map<void *, void *> graphOf_;
-  void destroy_exec(void *exec);
   int unroll_ = 1;
   bool spinSync_ = true;
-  size_t graphNodes_ = 0, graphEdges_ = 0;
-  struct Slot {
-    Sequence seq;
-    void *exec = nullptr, *execU = nullptr;
-    size_t nodes = 0, edges = 0;
-    double expected = 0;
-  };
-  size_t slot_ = 0; // selected slot (prepare_many)
-  std::vector<Slot> slots_; // prepare_many: own the compiled graphs (graphExec_ borrows)
 
   double watchdogS_ = 0;
   double watchdogK_ = 50;

@@ -702,8 +702,7 @@ std::string HaloExchange::rccl_preflight(Ctrl &ctrl) {
   auto graph_step = [&](CaptureMode mode) -> std::string {
     std::string wrong;
     for (int form = 0; form < 2 && why.empty() && wrong.empty(); ++form) {
-      hipGraph_t graph = nullptr;
-      hipGraphExec_t exec = nullptr;
+      CompiledGraph cg;
       try {
         TZ_LOG(Debug, "rccl preflight: graph step, " << capture_mode_name(mode) << " capture, form " << form);
         {
@@ -724,10 +723,9 @@ std::string HaloExchange::rccl_preflight(Ctrl &ctrl) {
             }
           }
           gb.add(0, tail, [&](void *cs) { unpack_group(remote, cs); });
-          graph = static_cast<hipGraph_t>(gb.finish());
+          TZ_LOG(Debug, "rccl preflight: instantiate");
+          cg = CompiledGraph::instantiate(gb.finish());
         }
-        TZ_LOG(Debug, "rccl preflight: instantiate");
-        TZ_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
       } catch (const std::exception &e) {
         // a capture or instantiation error is not a broken transport: RCCL stays for eager runs
         wrong = e.what();
@@ -745,7 +743,7 @@ std::string HaloExchange::rccl_preflight(Ctrl &ctrl) {
         const int gens[2][2] = {{1, 2}, {3, 1}}; // (generations are 0..3; 0 is the search's)
         for (int launch = 1; launch <= 2 && why.empty() && wrong.empty(); ++launch) {
           init_grid(s, gens[form][launch - 1]);
-          TZ_HIP(hipGraphLaunch(exec, s));
+          cg.launch(s);
           if (!bounded_wait(s, limit)) {
             hung(what); // communicators aborted: RCCL is gone
           } else {
@@ -760,8 +758,7 @@ std::string HaloExchange::rccl_preflight(Ctrl &ctrl) {
         wrong = e.what();
         drain_after_error(wrong);
       }
-      if (exec) (void)hipGraphExecDestroy(exec);
-      if (graph) (void)hipGraphDestroy(graph);
+      cg.reset();
       // every rank goes on to the next form (or stops) together
       double f[2] = {why.empty() ? 0.0 : 1.0, wrong.empty() ? 0.0 : 1.0};
       ctrl.allreduce_max(f, 2);

@@ -847,8 +847,7 @@ void DistSpmv::rccl_graph_preflight(Ctrl &ctrl) {
   bool chosen = false, hung = false;
   for (CaptureMode mode : modes) {
     std::string wrong;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
+    CompiledGraph cg;
     try {
       {
         GraphBuilder gb({s}, mode);
@@ -856,9 +855,8 @@ void DistSpmv::rccl_graph_preflight(Ctrl &ctrl) {
           scatter(cs);
           exchange(cs);
         });
-        graph = static_cast<hipGraph_t>(gb.finish());
+        cg = CompiledGraph::instantiate(gb.finish());
       }
-      TZ_HIP(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
     } catch (const std::exception &e) {
       wrong = e.what(); // a capture or instantiation error: RCCL stays for eager runs
     }
@@ -871,7 +869,7 @@ void DistSpmv::rccl_graph_preflight(Ctrl &ctrl) {
       for (int gen = 1; gen <= 2 && wrong.empty() && !hung; ++gen) {
         upload_x(gen);
         TZ_HIP(hipMemsetAsync(dXr_.get(), 0, dXr_.bytes(), s));
-        TZ_HIP(hipGraphLaunch(exec, s));
+        cg.launch(s);
         if (!wait()) {
           hung = true;
           break;
@@ -887,8 +885,7 @@ void DistSpmv::rccl_graph_preflight(Ctrl &ctrl) {
       wrong = e.what(); // a capture or instantiation error: RCCL stays for eager runs
       if (!wait()) hung = true;
     }
-    if (exec) (void)hipGraphExecDestroy(exec);
-    if (graph) (void)hipGraphDestroy(graph);
+    cg.reset();
     double flags[2] = {hung ? 1.0 : 0.0, wrong.empty() ? 0.0 : 1.0};
     ctrl.allreduce_max(flags, 2);
     if (flags[0] != 0.0) {

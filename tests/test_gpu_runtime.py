@@ -185,6 +185,96 @@ def test_benchmark_many_graph_slots(tz, gpu):
         assert halo.check_grid() == 0
 
 
+def test_graph_exec_ownership_interleavings(tz, gpu):
+    """prepare / prepare_many / select / precompile / set_graph_unroll / set_mode / destruction in
+    every order the runtime's callers use: each slot's ops count into a row of their own, so a
+    launch of another slot's graph, or of a remainder graph left over from another slot, unroll
+    or schedule, shows up in the wrong row. After every run each row holds exactly the
+    iterations run with its slot selected."""
+    torch = pytest.importorskip("torch")
+    n = 4096
+    ones = torch.ones(n, dtype=torch.float64, device="cuda")
+    y = torch.zeros(3, 3, n, dtype=torch.float64, device="cuda")  # [slot, op, element]
+    torch.cuda.synchronize()
+    K = tz._tz.kernels
+    Graph, Eager = tz.ExecMode.Graph, tz.ExecMode.Eager
+
+    def schedule(k, capturable=True):
+        def adder(i):
+            return lambda stream: K.axpy_f64(n, 1.0, ones.data_ptr(), y[k, i].data_ptr(), stream)
+
+        g = tz.Graph()
+        a, b, c = (tz.PyGpuOp(name, adder(i), 0.0, capturable) for i, name in enumerate("abc"))
+        g.start_then(a)
+        g.then(a, b)
+        g.then(a, c)
+        g.then_finish(b)
+        g.then_finish(c)
+        return tz.random_rollout(tz.State(g, tz.Platform(2)), k)
+
+    s0, s1, s2 = (schedule(k) for k in range(3))
+    want = [0, 0, 0]  # iterations run so far with slot k selected
+    rt = tz.HipRuntime(device=0, n_streams=2, mode=Graph, graph_unroll=3)
+
+    def run(k, iterations):
+        rt.run(iterations)
+        rt.device_sync()
+        want[k] += iterations
+        rows = torch.tensor(want, dtype=torch.float64, device="cuda")[:, None, None]
+        assert torch.equal(y, rows.expand_as(y)), (want, y[:, :, 0])
+
+    # 1. every slot in turn, with its own remainder graph (8 % 3 = 2) and beside it (7 % 3 = 1)
+    rt.prepare_many([s0, s1, s2])
+    for k in (0, 2, 1, 2):
+        rt.select(k)
+        rt.precompile(8)
+        assert rt.effective_mode == Graph
+        run(k, 8)
+        run(k, 7)
+        assert rt.effective_mode == Graph
+    # 2. a remainder graph does not survive a change of slot
+    rt.select(1)
+    rt.precompile(8)
+    rt.select(0)
+    run(0, 8)
+    # 3. a failed select changes nothing
+    with pytest.raises(Exception, match="out of range"):
+        rt.select(3)
+    run(0, 3)
+    # 4. a new unroll drops every slot; the same unroll again drops nothing
+    rt.set_graph_unroll(2)
+    assert rt.effective_mode == Eager
+    rt.prepare(s1)
+    rt.precompile(5)
+    run(1, 5)
+    assert rt.effective_mode == Graph
+    rt.set_graph_unroll(2)
+    assert rt.effective_mode == Graph
+    # 5. through eager mode and back
+    rt.set_mode(Eager)
+    rt.prepare(s0)
+    run(0, 2)
+    rt.set_mode(Graph)
+    rt.prepare_many([s2, s0])
+    rt.select(1)
+    run(0, 4)
+    # 6. a schedule that cannot be captured is an eager slot among graph slots
+    rt.prepare_many([s0, schedule(1, capturable=False), s2])
+    for k, mode in enumerate((Graph, Eager, Graph)):
+        rt.select(k)
+        assert rt.effective_mode == mode
+        run(k, 4)
+    # 7. destruction with slots and a remainder graph alive, then a new runtime
+    rt.set_graph_unroll(3)
+    rt.prepare_many([s0, s1, s2])
+    rt.select(2)
+    rt.precompile(8)
+    del rt
+    rt = tz.HipRuntime(device=0, n_streams=2, mode=Graph, graph_unroll=3)
+    rt.prepare(s0)
+    run(0, 3)
+
+
 def test_halo_rccl_self_exchange(tz, gpu):
     """RCCL transport on a 1-rank communicator (self send/recv in a group)."""
     halo, g = _small_halo(tz, neighbors=6, transport="rccl")
