@@ -4,6 +4,7 @@
   python -m tenzing_amd search --workload spmv --solver dfs --max-seqs 15000 --csv spmv.csv
   python -m tenzing_amd search --workload halo --replay halo.csv      # MCTS on recorded timings
   python -m tenzing_amd search --workload fused --sim                  # hardware-free (cost model)
+  python -m tenzing_amd search --workload cg --mode graph              # one CG iteration per run
   python -m tenzing_amd search --workload halo --save-best best.json   # search once ...
   python -m tenzing_amd run best.json --iters 1000                     # ... deploy many times
   python -m tenzing_amd rules spmv.csv --out spmv_                     # design rules
@@ -24,7 +25,8 @@ import time
 
 def _build_workload(a, ctrl, device, setup):
     import tenzing_amd as tz
-    from tenzing_amd.models import HaloConfig, SpmvConfig, build_fused, build_halo, build_spmv
+    from tenzing_amd.models import (CgConfig, HaloConfig, SpmvConfig, build_cg, build_fused,
+                                    build_halo, build_spmv)
 
     grid = ()
     if a.rank_grid:
@@ -56,6 +58,9 @@ def _build_workload(a, ctrl, device, setup):
     if a.workload == "fused":
         h, s, g = build_fused(hc, sc, ctrl, device, setup, horizontal=a.horizontal == "on")
         return g, {"halo": h, "spmv": s}
+    if a.workload == "cg":
+        c, g = build_cg(CgConfig(m=a.cg_m, form=a.cg_form, matrix=a.cg_matrix), ctrl, device, setup)
+        return g, {"cg": c}
     if a.workload == "noop":
         # reference test/test_noop_graph.cpp: Start -> op1 -> Finish (here: `--noop-width`
         # independent no-ops, so DFS has orderings and stream choices to enumerate)
@@ -213,7 +218,7 @@ _WORKLOAD_KEYS = ("workload", "noop_width", "streams", "halo_n", "nq", "ghost", 
                   "ipc_grid", "copy_puts", "copy_engines", "move_pairs", "horizontal",
                   "stencil", "rank_grid",
                   "spmv_m", "spmv_matrix", "spmv_form", "spmv_transport", "spmv_library",
-                  "spmv_distribute",
+                  "spmv_distribute", "cg_m", "cg_form", "cg_matrix", "cg_check_iters",
                   "cu_partition", "stream_priorities")
 
 
@@ -298,9 +303,12 @@ def cmd_run(a) -> int:
         wl["halo"].init_grid()
     if "spmv" in wl:
         wl["spmv"].reset_y()
+    if "cg" in wl:
+        wl["cg"].reset()
     rt.device_sync()
     rt.prepare(seq)
-    rt.run(1)
+    # one run before the checks; CG: exactly the iterations its host reference runs
+    rt.run(w.cg_check_iters if "cg" in wl else 1)
     rt.device_sync()
     out = {"schedule": a.schedule, "workload": w.workload, "ranks": ctrl.size,
            "streams": w.streams, "mode": "graph" if rt.effective_mode == tz.ExecMode.Graph
@@ -318,10 +326,17 @@ def cmd_run(a) -> int:
     if "spmv" in wl:
         out["spmv_max_rel_err"] = ctrl.allreduce_max([wl["spmv"].check()])[0]
         ok &= out["spmv_max_rel_err"] < 1e-4
+    if "cg" in wl:
+        # x after cg_check_iters iterations against the same iterations in f64 on the host
+        out["cg_check_iters"] = w.cg_check_iters
+        out["cg_max_rel_err"] = wl["cg"].check(w.cg_check_iters)
+        ok &= out["cg_max_rel_err"] < 1e-4
     rt.precompile(a.warmup)
     rt.run(a.warmup)
     rt.precompile(a.iters)  # the remainder of the unroll as one graph, compiled before timing
     rt.device_sync()
+    if "cg" in wl:
+        wl["cg"].reset()  # the timed iterations start from x = 0
     ctrl.barrier()
     t0 = time.perf_counter()
     rt.run(a.iters)
@@ -406,7 +421,7 @@ def _parser() -> argparse.ArgumentParser:
     sub = ap.add_subparsers(dest="cmd", required=True)
     s = sub.add_parser("search")
     s.add_argument("--workload", default="halo",
-                   choices=["halo", "spmv", "fused", "diamond", "noop"])
+                   choices=["halo", "spmv", "fused", "cg", "diamond", "noop"])
     s.add_argument("--noop-width", type=int, default=1)
     s.add_argument("--host", action="store_true",
                    help="time schedules on the host executor (CPU-only graphs)")
@@ -512,6 +527,15 @@ def _parser() -> argparse.ArgumentParser:
     s.add_argument("--spmv-distribute", default="auto", choices=["auto", "root", "local"],
                    help="several ranks: rank 0 builds / reads the matrix and sends each rank its "
                         "rows (root, the reference's setup) or every rank builds it (local)")
+    s.add_argument("--cg-m", type=int, default=150_000,
+                   help="cg (one rank): rows of the symmetric positive definite band matrix")
+    s.add_argument("--cg-form", default="choice", choices=["choice", "plain", "fused"],
+                   help="cg: one kernel per step (plain, 8 launches), fused (4 launches) or both "
+                        "as a ChoiceOp")
+    s.add_argument("--cg-matrix", default="",
+                   help="cg: symmetric Matrix Market file instead of the band matrix")
+    s.add_argument("--cg-check-iters", type=int, default=25,
+                   help="cg, `run`: iterations checked against the host's f64 CG (cg_max_rel_err)")
     s.set_defaults(fn=cmd_search)
     r = sub.add_parser("rules")
     r.add_argument("results")

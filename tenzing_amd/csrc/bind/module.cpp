@@ -2,6 +2,7 @@
 // The reference listed Python bindings as a roadmap item (README.md:56-58); here they are the
 // primary scripting surface, while the search engine itself stays native.
 #include <pybind11/functional.h>
+#include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
 
@@ -1171,6 +1172,51 @@ PYBIND11_MODULE(_tz, m) {
     CsrHost a = random_band_matrix(n, bw, nnz, seed);
     return py::make_tuple(a.rowPtr, a.colInd, a.val);
   });
+  m.def("spd_band_matrix", [](int64_t n, int64_t bw, int64_t nnz, uint64_t seed) {
+    CsrHost a = spd_band_matrix(n, bw, nnz, seed);
+    return py::make_tuple(a.rowPtr, a.colInd, a.val);
+  }, py::arg("n"), py::arg("bw"), py::arg("nnz"), py::arg("seed"),
+     "symmetric, strictly diagonally dominant band matrix (mirrored random_band_matrix off-diagonals, "
+     "a_ii = 1 + sum |a_ij|) as (rowPtr, colInd, val)");
+  py::class_<CgArgs>(m, "CgArgs")
+      .def(py::init<>())
+      .def_readwrite("m", &CgArgs::m)
+      .def_readwrite("bw", &CgArgs::bw)
+      .def_readwrite("nnz", &CgArgs::nnz)
+      .def_readonly("nnz_actual", &CgArgs::nnz_actual)
+      .def_readwrite("seed", &CgArgs::seed)
+      .def_readwrite("matrix", &CgArgs::matrix)
+      .def_readwrite("device", &CgArgs::device)
+      .def_readwrite("form", &CgArgs::form)
+      .def_readwrite("lanes", &CgArgs::lanes)
+      .def_readwrite("rhs", &CgArgs::rhs)
+      .def_readwrite("prefix", &CgArgs::prefix)
+      .def_readwrite("rank", &CgArgs::rank)
+      .def_readwrite("size", &CgArgs::size)
+      .def("json", [](const CgArgs &a) { return a.json().dump(); });
+  {
+    auto f32 = [](const std::vector<float> &v) { return py::array_t<float>(py::ssize_t(v.size()), v.data()); };
+    py::class_<ConjugateGradient, std::shared_ptr<ConjugateGradient>>(m, "ConjugateGradient")
+        .def(py::init([](const CgArgs &a) { return std::make_shared<ConjugateGradient>(a); }), py::arg("args"))
+        .def_property_readonly("args", &ConjugateGradient::args)
+        .def("rows", &ConjugateGradient::rows)
+        .def("matrix", [](const ConjugateGradient &c) {
+          const CsrHost &a = c.matrix();
+          return py::make_tuple(a.rowPtr, a.colInd, a.val);
+        }, "the system matrix as (rowPtr, colInd, val)")
+        .def("setup", &ConjugateGradient::setup, py::call_guard<py::gil_scoped_release>())
+        .def("ready", &ConjugateGradient::ready)
+        .def("add_to_graph", &ConjugateGradient::add_to_graph)
+        .def("reset", &ConjugateGradient::reset, py::call_guard<py::gil_scoped_release>(),
+             "x = 0, r = p = b, rr = b . b (synchronous)")
+        .def("x", [f32](const ConjugateGradient &c) { return f32(c.x()); })
+        .def("r", [f32](const ConjugateGradient &c) { return f32(c.r()); })
+        .def("p", [f32](const ConjugateGradient &c) { return f32(c.p()); })
+        .def("b", [f32](const ConjugateGradient &c) { return f32(c.b()); })
+        .def("rr", &ConjugateGradient::rr, "r . r of the current residual (f64, the kernels' summation order)")
+        .def("check", &ConjugateGradient::check, py::arg("k"), py::call_guard<py::gil_scoped_release>(),
+             "max |x - x_ref| / max |x_ref| against k host iterations in f64");
+  }
   m.def("read_matrix_market", [](const std::string &path) {
     CsrHost a = read_matrix_market(path);
     return py::make_tuple(a.rows, a.cols, a.rowPtr, a.colInd, a.val);
@@ -1254,6 +1300,60 @@ PYBIND11_MODULE(_tz, m) {
   k.def("set_stencil_xcd_tiles", [](bool on) { kern::stencil_tuning().xcd_tiles = on; }, py::arg("on"),
         "stencil tiles in XCD-contiguous order (each XCD a contiguous range of tiles)");
   k.def("get_stencil_xcd_tiles", []() { return kern::stencil_tuning().xcd_tiles; });
+  // conjugate-gradient kernels (cg_kernels.hip)
+  k.attr("CG_MAX_PARTIALS") = kern::kCgMaxPartials;
+  k.attr("SPMV_ILP") = kern::kSpmvIlp;
+  k.def("dot_partial_count", &kern::dot_partial_count, py::arg("n"));
+  k.def("spmv_dot_partial_count", &kern::spmv_dot_partial_count, py::arg("n_rows"), py::arg("lanes"));
+  k.def("dot_partials_f32", [](int64_t n, uintptr_t u, uintptr_t v, uintptr_t part, uintptr_t s) {
+    kern::dot_partials_f32(n, reinterpret_cast<const float *>(u), reinterpret_cast<const float *>(v),
+                           reinterpret_cast<double *>(part), P(s));
+  }, py::arg("n"), py::arg("u"), py::arg("v"), py::arg("partials"), py::arg("stream") = 0);
+  k.def("sum_partials_f64", [](uintptr_t part, int np, uintptr_t out, uintptr_t s) {
+    kern::sum_partials_f64(reinterpret_cast<const double *>(part), np, reinterpret_cast<double *>(out), P(s));
+  }, py::arg("partials"), py::arg("np"), py::arg("out"), py::arg("stream") = 0);
+  k.def("cg_alpha", [](uintptr_t part, int np, uintptr_t rr, uintptr_t alpha, uintptr_t s) {
+    kern::cg_alpha(reinterpret_cast<const double *>(part), np, reinterpret_cast<const double *>(rr),
+                   reinterpret_cast<double *>(alpha), P(s));
+  }, py::arg("partials_pq"), py::arg("np"), py::arg("rr"), py::arg("alpha"), py::arg("stream") = 0);
+  k.def("cg_beta", [](uintptr_t part, int np, uintptr_t rr, uintptr_t beta, uintptr_t s) {
+    kern::cg_beta(reinterpret_cast<const double *>(part), np, reinterpret_cast<double *>(rr),
+                  reinterpret_cast<double *>(beta), P(s));
+  }, py::arg("partials_rr"), py::arg("np"), py::arg("rr"), py::arg("beta"), py::arg("stream") = 0);
+  k.def("axpy_dev_f32", [](int64_t n, uintptr_t sc, int sign, uintptr_t x, uintptr_t y, uintptr_t s) {
+    kern::axpy_dev_f32(n, reinterpret_cast<const double *>(sc), sign, reinterpret_cast<const float *>(x),
+                       reinterpret_cast<float *>(y), P(s));
+  }, py::arg("n"), py::arg("scalar"), py::arg("sign"), py::arg("x"), py::arg("y"), py::arg("stream") = 0);
+  k.def("xpay_dev_f32", [](int64_t n, uintptr_t sc, uintptr_t x, uintptr_t y, uintptr_t s) {
+    kern::xpay_dev_f32(n, reinterpret_cast<const double *>(sc), reinterpret_cast<const float *>(x),
+                       reinterpret_cast<float *>(y), P(s));
+  }, py::arg("n"), py::arg("scalar"), py::arg("x"), py::arg("y"), py::arg("stream") = 0);
+  k.def("csr_spmv_dot", [](int n, uintptr_t rp, uintptr_t ci, uintptr_t v, uintptr_t p, uintptr_t q, int lanes,
+                           uintptr_t pq, uintptr_t prr, int npRr, uintptr_t rr, uintptr_t s) {
+    kern::csr_spmv_dot(n, reinterpret_cast<const int32_t *>(rp), reinterpret_cast<const int32_t *>(ci),
+                       reinterpret_cast<const float *>(v), reinterpret_cast<const float *>(p),
+                       reinterpret_cast<float *>(q), lanes, reinterpret_cast<double *>(pq),
+                       reinterpret_cast<const double *>(prr), npRr, reinterpret_cast<double *>(rr), P(s));
+  }, py::arg("n_rows"), py::arg("row_ptr"), py::arg("col_ind"), py::arg("val"), py::arg("p"), py::arg("q"),
+     py::arg("lanes"), py::arg("partials_pq"), py::arg("partials_rr") = 0, py::arg("np_rr") = 0,
+     py::arg("rr") = 0, py::arg("stream") = 0);
+  k.def("cg_fused_x", [](int64_t n, uintptr_t pq, int np, uintptr_t rr, uintptr_t p, uintptr_t x, uintptr_t s) {
+    kern::cg_fused_x(n, reinterpret_cast<const double *>(pq), np, reinterpret_cast<const double *>(rr),
+                     reinterpret_cast<const float *>(p), reinterpret_cast<float *>(x), P(s));
+  }, py::arg("n"), py::arg("partials_pq"), py::arg("np"), py::arg("rr"), py::arg("p"), py::arg("x"),
+     py::arg("stream") = 0);
+  k.def("cg_fused_r", [](int64_t n, uintptr_t pq, int np, uintptr_t rr, uintptr_t q, uintptr_t r, uintptr_t prr,
+                         uintptr_t s) {
+    kern::cg_fused_r(n, reinterpret_cast<const double *>(pq), np, reinterpret_cast<const double *>(rr),
+                     reinterpret_cast<const float *>(q), reinterpret_cast<float *>(r),
+                     reinterpret_cast<double *>(prr), P(s));
+  }, py::arg("n"), py::arg("partials_pq"), py::arg("np"), py::arg("rr"), py::arg("q"), py::arg("r"),
+     py::arg("partials_rr"), py::arg("stream") = 0);
+  k.def("cg_fused_p", [](int64_t n, uintptr_t prr, int np, uintptr_t rr, uintptr_t r, uintptr_t p, uintptr_t s) {
+    kern::cg_fused_p(n, reinterpret_cast<const double *>(prr), np, reinterpret_cast<const double *>(rr),
+                     reinterpret_cast<const float *>(r), reinterpret_cast<float *>(p), P(s));
+  }, py::arg("n"), py::arg("partials_rr"), py::arg("np"), py::arg("rr"), py::arg("r"), py::arg("p"),
+     py::arg("stream") = 0);
   k.def("gather_f32", [](int n, uintptr_t src, uintptr_t idx, uintptr_t dst, uintptr_t s) {
     kern::gather_f32(n, reinterpret_cast<const float *>(src), reinterpret_cast<const int32_t *>(idx),
                      reinterpret_cast<float *>(dst), P(s));

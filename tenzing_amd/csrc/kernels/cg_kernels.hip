@@ -1,0 +1,370 @@
+// Conjugate-gradient kernels for gfx950: dot products, vector updates whose coefficient lives in
+// device memory, and the fused forms (SpMV + dot, update + dot). Not in the reference.
+//
+// Vectors are f32; dot products accumulate in f64 (the product of two f32 values is exact in
+// f64); every scalar (rr, alpha, beta) is an f64 in device memory, so no launch argument carries
+// a value computed on the GPU and a whole iteration captures into a hipGraph.
+//
+// Two rules hold for every kernel here:
+//  1. Deterministic results. The element -> thread -> partial mapping depends only on n (never on
+//     pointer alignment), every sum has a fixed order, and there are no floating-point atomics.
+//  2. No hand-off between workgroups inside a launch (no tickets, no last-block reduce, no
+//     spinning). A reduction ends at a launch boundary: a kernel writes one partial per block,
+//     and the kernel that needs the scalar sums the partials itself in its prologue
+//     (sum_partials: every block in the same order, hence the same bits in every block).
+//
+// Layout of a vector pass (dot_partials_f32 and every update): the vector is cut into quads of 4
+// elements; quad k belongs to thread k % T of the pass k / T (T = blocks * 256), and the n % 4
+// tail elements to threads 0.. of block 0. Aligned pointers move a quad with one 16-B access,
+// others with four 4-B accesses; the arithmetic is the same.
+#include <hip/hip_runtime.h>
+
+#include "kernels.hpp"
+#include "spmv_device.hpp"
+
+#include <algorithm>
+#include <stdexcept>
+#include <string>
+
+namespace tz {
+namespace kern {
+
+namespace {
+
+#define TZ_HIP_LAUNCH_CHECK()                                                                      \
+  do {                                                                                             \
+    hipError_t e_ = hipGetLastError();                                                             \
+    if (e_ != hipSuccess)                                                                          \
+      throw std::runtime_error(std::string("kernel launch failed: ") + hipGetErrorString(e_));     \
+  } while (0)
+
+constexpr int kThreads = 256;      // vector and scalar kernels
+constexpr int kSpmvThreads = 1024; // csr_spmv_dot: at most 256 blocks must cover the chip
+
+// Sum of one value per thread, returned to every thread: xor butterfly inside each wave64 (all
+// lanes end with the same bits: a + b == b + a), then the waves' sums in wave order.
+template <int NW> __device__ __forceinline__ double block_sum(double v, double *sh) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double s = sh[0];
+#pragma unroll
+  for (int w = 1; w < NW; ++w) s += sh[w];
+  __syncthreads(); // sh may be reused
+  return s;
+}
+
+// The launch-boundary reduce: the sum of np <= 256 partials, the same bits in every thread of
+// every block that calls it (thread t holds partial t, or +0.0 from np on)
+template <int NW> __device__ __forceinline__ double sum_partials(const double *partials, int np, double *sh) {
+  const double v = int(threadIdx.x) < np ? partials[threadIdx.x] : 0.0;
+  return block_sum<NW>(v, sh);
+}
+
+__device__ __forceinline__ bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+__device__ __forceinline__ float4 load_quad(const float *p, int64_t k, bool al) {
+  if (al) return reinterpret_cast<const float4 *>(p)[k];
+  const float *s = p + 4 * k;
+  return make_float4(s[0], s[1], s[2], s[3]);
+}
+
+__device__ __forceinline__ void store_quad(float *p, int64_t k, bool al, float4 v) {
+  if (al) {
+    reinterpret_cast<float4 *>(p)[k] = v;
+    return;
+  }
+  float *d = p + 4 * k;
+  d[0] = v.x, d[1] = v.y, d[2] = v.z, d[3] = v.w;
+}
+
+__device__ __forceinline__ double dot_quad(double acc, float4 a, float4 b) {
+  acc += double(a.x) * double(b.x);
+  acc += double(a.y) * double(b.y);
+  acc += double(a.z) * double(b.z);
+  acc += double(a.w) * double(b.w);
+  return acc;
+}
+
+__global__ __launch_bounds__(kThreads) void dot_partials_k(int64_t n, const float *u, const float *v,
+                                                           double *__restrict__ partials) {
+  __shared__ double sh[kThreads / 64];
+  const bool au = aligned16(u), av = aligned16(v);
+  const int64_t nq = n / 4, stride = int64_t(gridDim.x) * kThreads;
+  double acc = 0.0;
+  for (int64_t k = int64_t(blockIdx.x) * kThreads + threadIdx.x; k < nq; k += stride)
+    acc = dot_quad(acc, load_quad(u, k, au), load_quad(v, k, av));
+  const int64_t t = nq * 4 + threadIdx.x;
+  if (blockIdx.x == 0 && t < n) acc += double(u[t]) * double(v[t]);
+  const double s = block_sum<kThreads / 64>(acc, sh);
+  if (threadIdx.x == 0) partials[blockIdx.x] = s;
+}
+
+__global__ __launch_bounds__(kThreads) void sum_partials_k(const double *__restrict__ partials, int np,
+                                                           double *__restrict__ out) {
+  __shared__ double sh[kThreads / 64];
+  const double s = sum_partials<kThreads / 64>(partials, np, sh);
+  if (threadIdx.x == 0) *out = s;
+}
+
+__device__ __forceinline__ double guarded_div(double num, double den) { return den != 0.0 ? num / den : 0.0; }
+
+__global__ __launch_bounds__(kThreads) void cg_alpha_k(const double *__restrict__ partialsPq, int np,
+                                                       const double *__restrict__ rr,
+                                                       double *__restrict__ alpha) {
+  __shared__ double sh[kThreads / 64];
+  const double pq = sum_partials<kThreads / 64>(partialsPq, np, sh);
+  if (threadIdx.x == 0) *alpha = guarded_div(*rr, pq);
+}
+
+__global__ __launch_bounds__(kThreads) void cg_beta_k(const double *__restrict__ partialsRr, int np,
+                                                      double *__restrict__ rr, double *__restrict__ beta) {
+  __shared__ double sh[kThreads / 64];
+  const double rrNew = sum_partials<kThreads / 64>(partialsRr, np, sh);
+  if (threadIdx.x == 0) {
+    *beta = guarded_div(rrNew, *rr);
+    *rr = rrNew;
+  }
+}
+
+// y = fmaf(a, x, y) over this thread's elements; with `sq`, the sum of the squares of what it
+// stored (the partial of y . y, in dot_partials_k's order)
+template <bool SQ>
+__device__ __forceinline__ double axpy_pass(int64_t n, float a, const float *x, float *y) {
+  const bool ax = aligned16(x), ay = aligned16(y);
+  const int64_t nq = n / 4, stride = int64_t(gridDim.x) * kThreads;
+  double acc = 0.0;
+  for (int64_t k = int64_t(blockIdx.x) * kThreads + threadIdx.x; k < nq; k += stride) {
+    const float4 xv = load_quad(x, k, ax);
+    float4 yv = load_quad(y, k, ay);
+    yv.x = fmaf(a, xv.x, yv.x);
+    yv.y = fmaf(a, xv.y, yv.y);
+    yv.z = fmaf(a, xv.z, yv.z);
+    yv.w = fmaf(a, xv.w, yv.w);
+    store_quad(y, k, ay, yv);
+    if (SQ) acc = dot_quad(acc, yv, yv);
+  }
+  const int64_t t = nq * 4 + threadIdx.x;
+  if (blockIdx.x == 0 && t < n) {
+    const float yt = fmaf(a, x[t], y[t]);
+    y[t] = yt;
+    if (SQ) acc += double(yt) * double(yt);
+  }
+  return acc;
+}
+
+// y = fmaf(s, y, x)
+__device__ __forceinline__ void xpay_pass(int64_t n, float s, const float *x, float *y) {
+  const bool ax = aligned16(x), ay = aligned16(y);
+  const int64_t nq = n / 4, stride = int64_t(gridDim.x) * kThreads;
+  for (int64_t k = int64_t(blockIdx.x) * kThreads + threadIdx.x; k < nq; k += stride) {
+    const float4 xv = load_quad(x, k, ax);
+    float4 yv = load_quad(y, k, ay);
+    yv.x = fmaf(s, yv.x, xv.x);
+    yv.y = fmaf(s, yv.y, xv.y);
+    yv.z = fmaf(s, yv.z, xv.z);
+    yv.w = fmaf(s, yv.w, xv.w);
+    store_quad(y, k, ay, yv);
+  }
+  const int64_t t = nq * 4 + threadIdx.x;
+  if (blockIdx.x == 0 && t < n) y[t] = fmaf(s, y[t], x[t]);
+}
+
+__global__ __launch_bounds__(kThreads) void axpy_dev_k(int64_t n, const double *__restrict__ s, float sign,
+                                                       const float *x, float *y) {
+  axpy_pass<false>(n, sign * float(*s), x, y);
+}
+
+__global__ __launch_bounds__(kThreads) void xpay_dev_k(int64_t n, const double *__restrict__ s,
+                                                       const float *x, float *y) {
+  xpay_pass(n, float(*s), x, y);
+}
+
+// x += alpha p, alpha = rr / (sum of the pq partials) formed in the prologue
+__global__ __launch_bounds__(kThreads) void cg_fused_x_k(int64_t n, const double *__restrict__ partialsPq,
+                                                         int np, const double *__restrict__ rr,
+                                                         const float *p, float *x) {
+  __shared__ double sh[kThreads / 64];
+  const double alpha = guarded_div(*rr, sum_partials<kThreads / 64>(partialsPq, np, sh));
+  axpy_pass<false>(n, float(alpha), p, x);
+}
+
+// r -= alpha q (the same prologue) and the partials of the new r . r
+__global__ __launch_bounds__(kThreads) void cg_fused_r_k(int64_t n, const double *__restrict__ partialsPq,
+                                                         int np, const double *__restrict__ rr,
+                                                         const float *q, float *r,
+                                                         double *__restrict__ partialsRr) {
+  __shared__ double sh[kThreads / 64];
+  const double alpha = guarded_div(*rr, sum_partials<kThreads / 64>(partialsPq, np, sh));
+  const double acc = axpy_pass<true>(n, -float(alpha), q, r);
+  const double s = block_sum<kThreads / 64>(acc, sh);
+  if (threadIdx.x == 0) partialsRr[blockIdx.x] = s;
+}
+
+// p = r + beta p, beta = (sum of the new rr partials) / rr formed in the prologue
+__global__ __launch_bounds__(kThreads) void cg_fused_p_k(int64_t n, const double *__restrict__ partialsRr,
+                                                         int np, const double *__restrict__ rr,
+                                                         const float *r, float *p) {
+  __shared__ double sh[kThreads / 64];
+  const double beta = guarded_div(sum_partials<kThreads / 64>(partialsRr, np, sh), *rr);
+  xpay_pass(n, float(beta), r, p);
+}
+
+// q = A p with W lanes per row (dev::csr_spmv_ilp_sum, the arithmetic of csr_spmv's ILP kernel)
+// in a grid-stride loop over the rows, and the block's partial of p . q. Block 0 also refreshes
+// rr from the rr partials of the previous iteration's r update (partialsRr may be null).
+template <int W, int K>
+__global__ __launch_bounds__(kSpmvThreads) void csr_spmv_dot_k(int nRows, const int32_t *__restrict__ rowPtr,
+                                                               const int32_t *__restrict__ colInd,
+                                                               const float *__restrict__ val,
+                                                               const float *__restrict__ p,
+                                                               float *__restrict__ q,
+                                                               double *__restrict__ partialsPq,
+                                                               const double *__restrict__ partialsRr,
+                                                               int npRr, double *__restrict__ rr) {
+  __shared__ double sh[kSpmvThreads / 64];
+  if (partialsRr && blockIdx.x == 0) { // uniform in the block
+    const double s = sum_partials<kSpmvThreads / 64>(partialsRr, npRr, sh);
+    if (threadIdx.x == 0) *rr = s;
+  }
+  const int lane = threadIdx.x & (W - 1);
+  const int rowsPerPass = int(gridDim.x) * (kSpmvThreads / W);
+  double acc = 0.0;
+  // whole W-lane groups leave the loop together (W divides 64)
+  for (int row = (blockIdx.x * kSpmvThreads + threadIdx.x) / W; row < nRows; row += rowsPerPass) {
+    const float sum = dev::csr_spmv_ilp_sum<W, K>(row, lane, rowPtr, colInd, val, p);
+    if (lane == 0) {
+      q[row] = sum;
+      acc += double(p[row]) * double(sum);
+    }
+  }
+  const double s = block_sum<kSpmvThreads / 64>(acc, sh);
+  if (threadIdx.x == 0) partialsPq[blockIdx.x] = s;
+}
+
+void check_vec(const char *what, int64_t n, const void *a, const void *b) {
+  if (n <= 0) throw std::runtime_error(std::string(what) + ": n must be positive");
+  if (!a || !b) throw std::runtime_error(std::string(what) + ": null pointer");
+  if ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) % 4)
+    throw std::runtime_error(std::string(what) + ": vectors must be 4-byte aligned");
+}
+
+void check_np(const char *what, const void *partials, int np) {
+  if (!partials || np < 1 || np > kCgMaxPartials)
+    throw std::runtime_error(std::string(what) + ": 1.." + std::to_string(kCgMaxPartials) + " partials");
+}
+
+} // namespace
+
+int dot_partial_count(int64_t n) {
+  return int(std::min<int64_t>(kCgMaxPartials, std::max<int64_t>(1, (n + 4 * kThreads - 1) / (4 * kThreads))));
+}
+
+int spmv_dot_partial_count(int nRows, int lanes) {
+  const int64_t threads = int64_t(nRows) * (lanes > kSpmvIlp ? lanes - kSpmvIlp : lanes);
+  return int(std::min<int64_t>(kCgMaxPartials, std::max<int64_t>(1, (threads + kSpmvThreads - 1) / kSpmvThreads)));
+}
+
+void dot_partials_f32(int64_t n, const float *u, const float *v, double *partials, void *stream) {
+  check_vec("dot_partials_f32", n, u, v);
+  if (!partials) throw std::runtime_error("dot_partials_f32: null pointer");
+  hipLaunchKernelGGL(dot_partials_k, dim3(dot_partial_count(n)), dim3(kThreads), 0,
+                     static_cast<hipStream_t>(stream), n, u, v, partials);
+  TZ_HIP_LAUNCH_CHECK();
+}
+
+void sum_partials_f64(const double *partials, int np, double *out, void *stream) {
+  check_np("sum_partials_f64", partials, np);
+  if (!out) throw std::runtime_error("sum_partials_f64: null pointer");
+  hipLaunchKernelGGL(sum_partials_k, dim3(1), dim3(kThreads), 0, static_cast<hipStream_t>(stream), partials,
+                     np, out);
+  TZ_HIP_LAUNCH_CHECK();
+}
+
+void cg_alpha(const double *partialsPq, int np, const double *rr, double *alpha, void *stream) {
+  check_np("cg_alpha", partialsPq, np);
+  if (!rr || !alpha) throw std::runtime_error("cg_alpha: null pointer");
+  hipLaunchKernelGGL(cg_alpha_k, dim3(1), dim3(kThreads), 0, static_cast<hipStream_t>(stream), partialsPq, np,
+                     rr, alpha);
+  TZ_HIP_LAUNCH_CHECK();
+}
+
+void cg_beta(const double *partialsRr, int np, double *rr, double *beta, void *stream) {
+  check_np("cg_beta", partialsRr, np);
+  if (!rr || !beta) throw std::runtime_error("cg_beta: null pointer");
+  hipLaunchKernelGGL(cg_beta_k, dim3(1), dim3(kThreads), 0, static_cast<hipStream_t>(stream), partialsRr, np,
+                     rr, beta);
+  TZ_HIP_LAUNCH_CHECK();
+}
+
+void axpy_dev_f32(int64_t n, const double *s, int sign, const float *x, float *y, void *stream) {
+  check_vec("axpy_dev_f32", n, x, y);
+  if (!s || (sign != 1 && sign != -1)) throw std::runtime_error("axpy_dev_f32: scalar pointer and sign +-1");
+  hipLaunchKernelGGL(axpy_dev_k, dim3(dot_partial_count(n)), dim3(kThreads), 0,
+                     static_cast<hipStream_t>(stream), n, s, float(sign), x, y);
+  TZ_HIP_LAUNCH_CHECK();
+}
+
+void xpay_dev_f32(int64_t n, const double *s, const float *x, float *y, void *stream) {
+  check_vec("xpay_dev_f32", n, x, y);
+  if (!s) throw std::runtime_error("xpay_dev_f32: null pointer");
+  hipLaunchKernelGGL(xpay_dev_k, dim3(dot_partial_count(n)), dim3(kThreads), 0,
+                     static_cast<hipStream_t>(stream), n, s, x, y);
+  TZ_HIP_LAUNCH_CHECK();
+}
+
+void cg_fused_x(int64_t n, const double *partialsPq, int np, const double *rr, const float *p, float *x,
+                void *stream) {
+  check_vec("cg_fused_x", n, p, x);
+  check_np("cg_fused_x", partialsPq, np);
+  if (!rr) throw std::runtime_error("cg_fused_x: null pointer");
+  hipLaunchKernelGGL(cg_fused_x_k, dim3(dot_partial_count(n)), dim3(kThreads), 0,
+                     static_cast<hipStream_t>(stream), n, partialsPq, np, rr, p, x);
+  TZ_HIP_LAUNCH_CHECK();
+}
+
+void cg_fused_r(int64_t n, const double *partialsPq, int np, const double *rr, const float *q, float *r,
+                double *partialsRr, void *stream) {
+  check_vec("cg_fused_r", n, q, r);
+  check_np("cg_fused_r", partialsPq, np);
+  if (!rr || !partialsRr) throw std::runtime_error("cg_fused_r: null pointer");
+  hipLaunchKernelGGL(cg_fused_r_k, dim3(dot_partial_count(n)), dim3(kThreads), 0,
+                     static_cast<hipStream_t>(stream), n, partialsPq, np, rr, q, r, partialsRr);
+  TZ_HIP_LAUNCH_CHECK();
+}
+
+void cg_fused_p(int64_t n, const double *partialsRr, int np, const double *rr, const float *r, float *p,
+                void *stream) {
+  check_vec("cg_fused_p", n, r, p);
+  check_np("cg_fused_p", partialsRr, np);
+  if (!rr) throw std::runtime_error("cg_fused_p: null pointer");
+  hipLaunchKernelGGL(cg_fused_p_k, dim3(dot_partial_count(n)), dim3(kThreads), 0,
+                     static_cast<hipStream_t>(stream), n, partialsRr, np, rr, r, p);
+  TZ_HIP_LAUNCH_CHECK();
+}
+
+void csr_spmv_dot(int nRows, const int32_t *rowPtr, const int32_t *colInd, const float *val, const float *p,
+                  float *q, int lanes, double *partialsPq, const double *partialsRr, int npRr, double *rr,
+                  void *stream) {
+  if (nRows <= 0) throw std::runtime_error("csr_spmv_dot: nRows must be positive");
+  if (!rowPtr || !colInd || !val || !p || !q || !partialsPq)
+    throw std::runtime_error("csr_spmv_dot: null pointer");
+  if (partialsRr) {
+    check_np("csr_spmv_dot", partialsRr, npRr);
+    if (!rr) throw std::runtime_error("csr_spmv_dot: null pointer");
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int W = lanes - kSpmvIlp;
+  if (W != 1 && W != 2 && W != 4) throw std::runtime_error("csr_spmv_dot: lanes must be kSpmvIlp + 1, 2 or 4");
+  const dim3 g(unsigned(spmv_dot_partial_count(nRows, W))), b(kSpmvThreads);
+  switch (W) {
+  case 1: hipLaunchKernelGGL((csr_spmv_dot_k<1, 16>), g, b, 0, s, nRows, rowPtr, colInd, val, p, q, partialsPq, partialsRr, npRr, rr); break;
+  case 2: hipLaunchKernelGGL((csr_spmv_dot_k<2, 8>), g, b, 0, s, nRows, rowPtr, colInd, val, p, q, partialsPq, partialsRr, npRr, rr); break;
+  default: hipLaunchKernelGGL((csr_spmv_dot_k<4, 4>), g, b, 0, s, nRows, rowPtr, colInd, val, p, q, partialsPq, partialsRr, npRr, rr); break;
+  }
+  TZ_HIP_LAUNCH_CHECK();
+}
+
+} // namespace kern
+} // namespace tz

@@ -219,6 +219,49 @@ void gather_put_signal(const float *src, const int32_t *idx, const PutSeg *segs,
                        unsigned int *done, void *stream);
 /// y = a + b (f32, vectorized)
 void vector_add_f32(int n, const float *a, const float *b, float *y, void *stream);
+// ---- conjugate gradient (cg_kernels.hip): f32 vectors, f64 dot accumulation, every scalar an
+// f64 in device memory. Results are deterministic (fixed partial count and summation order, no
+// floating-point atomics) and no workgroup waits for another inside a launch: a dot product is
+// one partial per block, and whoever needs the scalar sums the partials in its prologue.
+/// partials per slab at most (a slab is kCgMaxPartials doubles, 2 KB)
+constexpr int kCgMaxPartials = 256;
+/// partials dot_partials_f32 / cg_fused_r write for vectors of n elements: ceil(n / 1024),
+/// clamped to [1, kCgMaxPartials]
+int dot_partial_count(int64_t n);
+/// partials csr_spmv_dot writes: ceil(nRows * W / 1024), clamped likewise (`lanes`: W or kSpmvIlp + W)
+int spmv_dot_partial_count(int nRows, int lanes);
+/// partials[b] = block b's share of u . v, b < dot_partial_count(n); u may equal v. Vectors need
+/// 4-byte alignment only (16-byte aligned ones are read with 16-byte loads, same results).
+void dot_partials_f32(int64_t n, const float *u, const float *v, double *partials, void *stream);
+/// *out = the sum of np partials, in the order every prologue uses: thread t of 256 holds
+/// partial t (+0.0 from np on), xor butterfly over each wave64 (offsets 32, 16, .. 1), then the
+/// four waves' sums in wave order. One block.
+void sum_partials_f64(const double *partials, int np, double *out, void *stream);
+/// alpha = pq != 0 ? rr / pq : 0 with pq the sum of the partials. One block.
+void cg_alpha(const double *partials_pq, int np, const double *rr, double *alpha, void *stream);
+/// rr_new = the sum of the partials; beta = rr != 0 ? rr_new / rr : 0; then rr = rr_new. One block.
+void cg_beta(const double *partials_rr, int np, double *rr, double *beta, void *stream);
+/// y[i] = fmaf(sign * float(*s), x[i], y[i]), sign = +1 or -1
+void axpy_dev_f32(int64_t n, const double *s, int sign, const float *x, float *y, void *stream);
+/// y[i] = fmaf(float(*s), y[i], x[i])
+void xpay_dev_f32(int64_t n, const double *s, const float *x, float *y, void *stream);
+/// q = A p as csr_spmv's ILP kernel computes it (lanes = kSpmvIlp + W, W = 1, 2, 4; same bits)
+/// and partials_pq[b] = block b's share of p . q, b < spmv_dot_partial_count(nRows, lanes).
+/// With partials_rr, block 0 also stores their sum to *rr (nothing in this launch reads rr).
+void csr_spmv_dot(int nRows, const int32_t *rowPtr, const int32_t *colInd, const float *val, const float *p,
+                  float *q, int lanes, double *partials_pq, const double *partials_rr, int np_rr, double *rr,
+                  void *stream);
+/// x += alpha p with alpha formed as cg_alpha does (same bits as cg_alpha + axpy_dev_f32)
+void cg_fused_x(int64_t n, const double *partials_pq, int np, const double *rr, const float *p, float *x,
+                void *stream);
+/// r -= alpha q (alpha likewise) and partials_rr = the partials of the new r . r (same bits as
+/// cg_alpha + axpy_dev_f32 + dot_partials_f32)
+void cg_fused_r(int64_t n, const double *partials_pq, int np, const double *rr, const float *q, float *r,
+                double *partials_rr, void *stream);
+/// p = r + beta p with beta = rr != 0 ? sum(partials_rr) / rr : 0 (rr is not written)
+void cg_fused_p(int64_t n, const double *partials_rr, int np, const double *rr, const float *r, float *p,
+                void *stream);
+
 /// y += alpha * x (f64)
 void axpy_f64(int64_t n, double alpha, const double *x, double *y, void *stream);
 /// fill a[i] = base + scale * i (f64) — deterministic test patterns

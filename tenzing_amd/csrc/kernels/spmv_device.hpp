@@ -15,15 +15,12 @@ namespace dev {
 // any (one pass covers W*K entries of the row). Short rows (10 entries on average here) then cost
 // one latency chain per row (row pointers -> columns -> x) with few, loaded waves, instead of one
 // chain per W entries on 4-8x as many waves. Whole W-lane groups exit together (W divides 64).
+// the row's sum, in every one of its W lanes (all W lanes of a row call this together)
 template <int W, int K>
-__device__ __forceinline__ void csr_spmv_ilp_row(int gtid, int nRows, const int32_t *__restrict__ rowPtr,
-                                                 const int32_t *__restrict__ colInd,
-                                                 const float *__restrict__ val,
-                                                 const float *__restrict__ x, float *__restrict__ y,
-                                                 int accumulate) {
-  const int row = gtid / W;
-  const int lane = gtid & (W - 1);
-  if (row >= nRows) return;
+__device__ __forceinline__ float csr_spmv_ilp_sum(int row, int lane, const int32_t *__restrict__ rowPtr,
+                                                  const int32_t *__restrict__ colInd,
+                                                  const float *__restrict__ val,
+                                                  const float *__restrict__ x) {
   const int b = rowPtr[row], e = rowPtr[row + 1];
   float sum = 0.f;
   for (int j0 = b + lane; j0 < e; j0 += W * K) {
@@ -45,6 +42,19 @@ __device__ __forceinline__ void csr_spmv_ilp_row(int gtid, int nRows, const int3
   }
 #pragma unroll
   for (int off = W / 2; off > 0; off >>= 1) sum += __shfl_xor(sum, off, W);
+  return sum;
+}
+
+template <int W, int K>
+__device__ __forceinline__ void csr_spmv_ilp_row(int gtid, int nRows, const int32_t *__restrict__ rowPtr,
+                                                 const int32_t *__restrict__ colInd,
+                                                 const float *__restrict__ val,
+                                                 const float *__restrict__ x, float *__restrict__ y,
+                                                 int accumulate) {
+  const int row = gtid / W;
+  const int lane = gtid & (W - 1);
+  if (row >= nRows) return;
+  const float sum = csr_spmv_ilp_sum<W, K>(row, lane, rowPtr, colInd, val, x);
   if (lane == 0) y[row] = accumulate ? y[row] + sum : sum;
 }
 

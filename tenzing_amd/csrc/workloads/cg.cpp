@@ -1,0 +1,318 @@
+// Conjugate gradient as a workload: one schedule run is one CG iteration on A x = b.
+//
+// Not in the reference (its SpMV workload is the single product y = A x). An iteration is one
+// SpMV, two global reductions and three vector updates; at 150,000 rows each kernel takes a few
+// microseconds, so which ops are fused and which run side by side decides the iteration time.
+//
+// Scalars (rr = r . r, alpha, beta) are f64 values in device memory and every dot product is a
+// slab of per-block partials that its consumer sums (kernels/cg_kernels.hip). Each scalar and
+// each slab has exactly one writer op per form, and the graph's edges keep that writer from
+// overlapping any reader:
+//   plain: alpha <- cg_alpha, beta and rr <- cg_beta, pq slab <- dot_pq, rr slab <- dot_rr
+//   fused: pq slab <- spmvdot, rr slab <- the r update, rr <- block 0 of the next iteration's
+//          spmvdot (after the last reader of the old rr, the p update, and before the first
+//          reader of the new one); alpha and beta live in registers only
+#include "workloads.hpp"
+
+#include "core/util.hpp"
+#include "hip/hip_runtime.hpp"
+
+#include <hip/hip_runtime_api.h>
+
+#include <algorithm>
+#include <cmath>
+#include <random>
+
+namespace tz {
+
+Json CgArgs::json() const {
+  Json j;
+  j["m"] = m;
+  j["bw"] = bw;
+  j["nnz"] = nnz;
+  j["nnz_actual"] = nnz_actual;
+  j["seed"] = int64_t(seed);
+  j["matrix"] = matrix;
+  j["form"] = form;
+  j["lanes"] = lanes;
+  j["rhs"] = rhs;
+  j["rank"] = rank;
+  j["size"] = size;
+  return j;
+}
+
+namespace {
+
+// the kernels' order (kern::sum_partials_f64): xor butterfly over each 64 partials, then the
+// four groups in order
+double sum_partials_host(const double *p, int np) {
+  double total = 0.0;
+  for (int w = 0; w < 4; ++w) {
+    double v[64], t[64];
+    for (int l = 0; l < 64; ++l) v[l] = w * 64 + l < np ? p[w * 64 + l] : 0.0;
+    for (int off = 32; off > 0; off >>= 1) {
+      for (int l = 0; l < 64; ++l) t[l] = v[l] + v[l ^ off];
+      std::copy(t, t + 64, v);
+    }
+    total = w == 0 ? v[0] : total + v[0];
+  }
+  return total;
+}
+
+using Body = void (ConjugateGradient::*)(void *) const;
+
+class CgOp : public GpuOp {
+public:
+  CgOp(std::shared_ptr<const ConjugateGradient> c, std::string name, std::string kind, Body body,
+       double latencyUs, double bytes, double rate)
+      : c_(std::move(c)), name_(std::move(name)), kind_(std::move(kind)), body_(body), lat_(latencyUs),
+        bytes_(bytes), rate_(rate) {}
+  std::string name() const override { return name_; }
+  std::string kind() const override { return kind_; }
+  double bytes() const override { return bytes_; }
+  // a launch plus its bytes at `rate_` bytes per microsecond (gathers run below streaming rate)
+  double cost_us() const override { return lat_ + bytes_ / rate_; }
+  std::vector<Traffic> traffic() const override {
+    if (bytes_ <= 0) return {};
+    return {{"hbm", "kernel", bytes_}};
+  }
+  double latency_us() const override { return lat_; }
+  void launch(void *st, Executor &) const override { ((*c_).*body_)(st); }
+
+private:
+  std::shared_ptr<const ConjugateGradient> c_;
+  std::string name_, kind_;
+  Body body_;
+  double lat_, bytes_, rate_;
+};
+
+} // namespace
+
+ConjugateGradient::ConjugateGradient(CgArgs a) : a_(std::move(a)) {
+  TZ_CHECK(a_.size == 1 && a_.rank == 0,
+           "the conjugate-gradient workload runs on one rank only (got rank " << a_.rank << " of " << a_.size
+               << "): several ranks need a halo of p and an allreduce per dot product");
+  TZ_CHECK(a_.form == "choice" || a_.form == "plain" || a_.form == "fused",
+           "CG form must be choice, plain or fused (got " << a_.form << ")");
+  TZ_CHECK(a_.rhs == "random" || a_.rhs == "zero", "CG rhs must be random or zero (got " << a_.rhs << ")");
+  if (!a_.matrix.empty()) {
+    A_ = read_matrix_market(a_.matrix);
+    TZ_CHECK(A_.rows == A_.cols, a_.matrix << ": CG needs a square matrix, got " << A_.rows << " x " << A_.cols);
+    // symmetric: every entry (r, c, v) has its mirror (c, r, v)
+    for (int64_t r = 0; r < A_.rows; ++r)
+      for (int32_t j = A_.rowPtr[size_t(r)]; j < A_.rowPtr[size_t(r + 1)]; ++j) {
+        const int32_t c = A_.colInd[size_t(j)];
+        const auto b0 = A_.colInd.begin() + A_.rowPtr[size_t(c)], b1 = A_.colInd.begin() + A_.rowPtr[size_t(c) + 1];
+        const auto it = std::lower_bound(b0, b1, int32_t(r));
+        TZ_CHECK(it != b1 && *it == int32_t(r) && A_.val[size_t(it - A_.colInd.begin())] == A_.val[size_t(j)],
+                 a_.matrix << ": not symmetric at (" << r + 1 << ", " << c + 1 << "): CG needs a symmetric "
+                           << "positive definite matrix");
+      }
+    a_.m = A_.rows;
+    a_.bw = 0;
+    a_.nnz = A_.nnz();
+  } else {
+    TZ_CHECK(a_.m > 0, "CG needs at least one row");
+    if (a_.bw <= 0) a_.bw = a_.m;
+    if (a_.nnz <= 0) a_.nnz = 5 * a_.m;
+    A_ = spd_band_matrix(a_.m, a_.bw, a_.nnz, a_.seed);
+  }
+  TZ_CHECK(A_.rows < (int64_t(1) << 31) / 4, "CG: too many rows");
+  a_.nnz_actual = A_.nnz();
+  b_.assign(size_t(A_.rows), 0.f);
+  if (a_.rhs == "random") {
+    // 24 random bits per entry: k / 2^23 - 1 is exact in f32 and lies in [-1, 1)
+    std::mt19937_64 rng(a_.seed ^ 0xC6A4A7935BD1E995ull);
+    for (float &v : b_) v = float(int64_t(rng() >> 40)) / 8388608.f - 1.f;
+  }
+  const int W = a_.lanes - kern::kSpmvIlp;
+  TZ_CHECK(a_.lanes == -1 || a_.lanes == 0 || W == 1 || W == 2 || W == 4 ||
+               (a_.lanes > 0 && a_.lanes <= 64 && (a_.lanes & (a_.lanes - 1)) == 0),
+           "CG lanes: a kern::csr_spmv variant (got " << a_.lanes << ")");
+}
+
+void ConjugateGradient::setup() {
+  if (ready()) return;
+  if (a_.device >= 0) TZ_HIP(hipSetDevice(a_.device));
+  auto up = [](DeviceBuffer &d, const void *p, size_t bytes) {
+    d = DeviceBuffer(std::max<size_t>(bytes, 16));
+    d.upload(p, bytes);
+  };
+  up(dRow_, A_.rowPtr.data(), A_.rowPtr.size() * 4);
+  up(dCol_, A_.colInd.data(), A_.colInd.size() * 4);
+  up(dVal_, A_.val.data(), A_.val.size() * 4);
+  up(dB_, b_.data(), b_.size() * 4);
+  const size_t vb = std::max<size_t>(size_t(rows()) * 4, 16);
+  dR_ = DeviceBuffer(vb);
+  dP_ = DeviceBuffer(vb);
+  dQ_ = DeviceBuffer(vb);
+  dScal_ = DeviceBuffer((2 * size_t(kern::kCgMaxPartials) + 3) * sizeof(double));
+  dX_ = DeviceBuffer(vb);
+  reset();
+}
+
+void ConjugateGradient::reset() {
+  TZ_CHECK(ready(), "CG not set up");
+  // synchronous: schedules run on non-blocking streams that do not order after the null stream
+  TZ_HIP(hipDeviceSynchronize());
+  const size_t vb = size_t(rows()) * 4;
+  TZ_HIP(hipMemset(dX_.get(), 0, dX_.bytes()));
+  TZ_HIP(hipMemset(dQ_.get(), 0, dQ_.bytes()));
+  TZ_HIP(hipMemset(dScal_.get(), 0, dScal_.bytes()));
+  TZ_HIP(hipMemcpy(dR_.get(), dB_.get(), vb, hipMemcpyDeviceToDevice));
+  TZ_HIP(hipMemcpy(dP_.get(), dB_.get(), vb, hipMemcpyDeviceToDevice));
+  kern::dot_partials_f32(rows(), dR_.as<float>(), dR_.as<float>(), rrp_(), nullptr);
+  kern::sum_partials_f64(rrp_(), np_vec(), rr_(), nullptr);
+  TZ_HIP(hipDeviceSynchronize());
+}
+
+std::vector<float> ConjugateGradient::down(const DeviceBuffer &d) const {
+  TZ_CHECK(ready(), "CG not set up");
+  TZ_HIP(hipDeviceSynchronize());
+  std::vector<float> v(static_cast<size_t>(rows()));
+  d.download(v.data(), v.size() * 4);
+  return v;
+}
+
+double ConjugateGradient::rr() const {
+  TZ_CHECK(ready(), "CG not set up");
+  TZ_HIP(hipDeviceSynchronize());
+  std::vector<double> part(static_cast<size_t>(kern::kCgMaxPartials), 0.0);
+  TZ_HIP(hipMemcpy(part.data(), rrp_(), part.size() * sizeof(double), hipMemcpyDeviceToHost));
+  return sum_partials_host(part.data(), np_vec());
+}
+
+double ConjugateGradient::check(int k) const {
+  const size_t n = size_t(rows());
+  std::vector<double> x(n, 0.0), r(b_.begin(), b_.end()), p(r), q(n);
+  double rr = 0;
+  for (size_t i = 0; i < n; ++i) rr += r[i] * r[i];
+  for (int it = 0; it < k; ++it) {
+    double pq = 0;
+    for (size_t i = 0; i < n; ++i) {
+      double s = 0;
+      for (int32_t j = A_.rowPtr[i]; j < A_.rowPtr[i + 1]; ++j)
+        s += double(A_.val[size_t(j)]) * p[size_t(A_.colInd[size_t(j)])];
+      q[i] = s;
+      pq += p[i] * s;
+    }
+    const double alpha = pq != 0.0 ? rr / pq : 0.0;
+    double rrNew = 0;
+    for (size_t i = 0; i < n; ++i) {
+      x[i] += alpha * p[i];
+      r[i] -= alpha * q[i];
+      rrNew += r[i] * r[i];
+    }
+    const double beta = rr != 0.0 ? rrNew / rr : 0.0;
+    rr = rrNew;
+    for (size_t i = 0; i < n; ++i) p[i] = r[i] + beta * p[i];
+  }
+  const std::vector<float> xd = this->x();
+  double err = 0, scale = 0;
+  for (size_t i = 0; i < n; ++i) {
+    err = std::max(err, std::abs(double(xd[i]) - x[i]));
+    scale = std::max(scale, std::abs(x[i]));
+  }
+  return scale > 0 ? err / scale : err;
+}
+
+// ------------------------------------------------------------------ op bodies
+
+void ConjugateGradient::spmv(void *s) const {
+  kern::csr_spmv(int(rows()), dRow_.as<int32_t>(), dCol_.as<int32_t>(), dVal_.as<float>(), dP_.as<float>(),
+                 dQ_.as<float>(), a_.lanes, false, s);
+}
+void ConjugateGradient::dot_pq(void *s) const {
+  kern::dot_partials_f32(rows(), dP_.as<float>(), dQ_.as<float>(), pq_(), s);
+}
+void ConjugateGradient::alpha(void *s) const { kern::cg_alpha(pq_(), np_vec(), rr_(), alpha_(), s); }
+void ConjugateGradient::update_x(void *s) const {
+  kern::axpy_dev_f32(rows(), alpha_(), +1, dP_.as<float>(), dX_.as<float>(), s);
+}
+void ConjugateGradient::update_r(void *s) const {
+  kern::axpy_dev_f32(rows(), alpha_(), -1, dQ_.as<float>(), dR_.as<float>(), s);
+}
+void ConjugateGradient::dot_rr(void *s) const {
+  kern::dot_partials_f32(rows(), dR_.as<float>(), dR_.as<float>(), rrp_(), s);
+}
+void ConjugateGradient::beta(void *s) const { kern::cg_beta(rrp_(), np_vec(), rr_(), beta_(), s); }
+void ConjugateGradient::update_p(void *s) const {
+  kern::xpay_dev_f32(rows(), beta_(), dR_.as<float>(), dP_.as<float>(), s);
+}
+void ConjugateGradient::fused_spmv_dot(void *s) const {
+  kern::csr_spmv_dot(int(rows()), dRow_.as<int32_t>(), dCol_.as<int32_t>(), dVal_.as<float>(), dP_.as<float>(),
+                     dQ_.as<float>(), kFusedLanes, pq_(), rrp_(), np_vec(), rr_(), s);
+}
+void ConjugateGradient::fused_x(void *s) const {
+  kern::cg_fused_x(rows(), pq_(), np_spmv(), rr_(), dP_.as<float>(), dX_.as<float>(), s);
+}
+void ConjugateGradient::fused_r(void *s) const {
+  kern::cg_fused_r(rows(), pq_(), np_spmv(), rr_(), dQ_.as<float>(), dR_.as<float>(), rrp_(), s);
+}
+void ConjugateGradient::fused_p(void *s) const {
+  kern::cg_fused_p(rows(), rrp_(), np_vec(), rr_(), dR_.as<float>(), dP_.as<float>(), s);
+}
+
+// ------------------------------------------------------------------ graph
+
+std::shared_ptr<Graph> ConjugateGradient::form_graph(bool fused) const {
+  auto self = shared_from_this();
+  const std::string p = a_.prefix + (fused ? "f_" : "");
+  const double n = double(rows());
+  // cost model: a launch of ~3 us plus the bytes at 4e6 bytes / us (the SpMV workload's
+  // VectorAdd), the SpMV's gathers at 3e6; a prologue that sums a slab adds a fraction of a us
+  auto op = [&](const char *name, const char *kind, Body body, double lat, double bytes, double rate = 4.0e6) {
+    return std::make_shared<CgOp>(self, p + name, kind, body, lat, bytes, rate);
+  };
+  auto g = std::make_shared<Graph>();
+  if (fused) {
+    auto sd = op("spmvdot", "CgSpmvDot", &ConjugateGradient::fused_spmv_dot, 4.5, spmv_bytes(), 3.0e6);
+    auto ux = op("x", "CgFusedAxpy", &ConjugateGradient::fused_x, 3.3, 12.0 * n);
+    auto ur = op("r", "CgFusedAxpyDot", &ConjugateGradient::fused_r, 3.5, 12.0 * n);
+    auto up = op("p", "CgFusedXpay", &ConjugateGradient::fused_p, 3.3, 12.0 * n);
+    g->start_then(sd);
+    g->then(sd, ux); // alpha: the pq partials (and q for the r update)
+    g->then(sd, ur);
+    g->then(ur, up); // beta: the rr partials, and the new r
+    g->then(ux, up); // p is overwritten after its readers (the SpMV through ux / ur)
+    g->then_finish(up);
+    return g;
+  }
+  auto sp = op("spmv", "CgSpmv", &ConjugateGradient::spmv, 4.0, spmv_bytes(), 3.0e6);
+  auto dpq = op("dot_pq", "CgDot", &ConjugateGradient::dot_pq, 3.0, 8.0 * n);
+  auto al = op("alpha", "CgScalar", &ConjugateGradient::alpha, 2.5, 0.0);
+  auto ux = op("x", "CgAxpy", &ConjugateGradient::update_x, 3.0, 12.0 * n);
+  auto ur = op("r", "CgAxpy", &ConjugateGradient::update_r, 3.0, 12.0 * n);
+  auto drr = op("dot_rr", "CgDot", &ConjugateGradient::dot_rr, 3.0, 4.0 * n);
+  auto be = op("beta", "CgScalar", &ConjugateGradient::beta, 2.5, 0.0);
+  auto up = op("p", "CgXpay", &ConjugateGradient::update_p, 3.0, 12.0 * n);
+  g->start_then(sp);
+  g->then(sp, dpq);
+  g->then(dpq, al);
+  g->then(al, ux);
+  g->then(al, ur);
+  g->then(sp, ur); // q is written before the r update reads it
+  g->then(ur, drr);
+  g->then(drr, be); // beta also rewrites rr: after alpha read it (alpha -> r -> dot_rr -> beta)
+  g->then(be, up);
+  g->then(ux, up); // p is overwritten after both of its readers
+  g->then(sp, up);
+  g->then_finish(up);
+  return g;
+}
+
+void ConjugateGradient::add_to_graph(Graph &g) {
+  const std::string &p = a_.prefix;
+  OpPtr top;
+  if (a_.form == "choice") {
+    std::vector<OpPtr> alts = {std::make_shared<StaticCompoundOp>(p + "plain", form_graph(false)),
+                               std::make_shared<StaticCompoundOp>(p + "fused", form_graph(true))};
+    top = std::make_shared<StaticChoiceOp>(p + "form", alts);
+  } else {
+    top = std::make_shared<StaticCompoundOp>(p + a_.form, form_graph(a_.form == "fused"));
+  }
+  g.start_then(top);
+  g.then_finish(top);
+}
+
+} // namespace tz

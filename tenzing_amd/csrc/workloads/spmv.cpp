@@ -84,6 +84,53 @@ CsrHost random_band_matrix(int64_t n, int64_t bw, int64_t nnz, uint64_t seed) {
   return A;
 }
 
+CsrHost spd_band_matrix(int64_t n, int64_t bw, int64_t nnz, uint64_t seed) {
+  const CsrHost B = random_band_matrix(n, bw, nnz, seed);
+  // one (pair, value) per unordered off-diagonal pair: the upper triangle's entry first, so a
+  // pair present on both sides keeps that value
+  struct Pair {
+    int64_t key; // lo * n + hi, lo < hi
+    bool lower;
+    float v;
+  };
+  std::vector<Pair> ps;
+  ps.reserve(size_t(B.nnz()));
+  for (int64_t r = 0; r < n; ++r)
+    for (int32_t j = B.rowPtr[size_t(r)]; j < B.rowPtr[size_t(r + 1)]; ++j) {
+      const int64_t c = B.colInd[size_t(j)];
+      if (c == r) continue;
+      ps.push_back({std::min(r, c) * n + std::max(r, c), c < r, B.val[size_t(j)]});
+    }
+  std::sort(ps.begin(), ps.end(), [](const Pair &a, const Pair &b) {
+    return a.key != b.key ? a.key < b.key : a.lower < b.lower;
+  });
+  std::vector<std::pair<int64_t, float>> e; // (row * n + col, value), both sides and the diagonal
+  e.reserve(2 * ps.size() + size_t(n));
+  std::vector<double> absSum(size_t(n), 0.0);
+  for (size_t k = 0; k < ps.size(); ++k) {
+    if (k > 0 && ps[k].key == ps[k - 1].key) continue;
+    const int64_t lo = ps[k].key / n, hi = ps[k].key % n;
+    e.emplace_back(lo * n + hi, ps[k].v);
+    e.emplace_back(hi * n + lo, ps[k].v);
+    absSum[size_t(lo)] += std::abs(double(ps[k].v));
+    absSum[size_t(hi)] += std::abs(double(ps[k].v));
+  }
+  for (int64_t i = 0; i < n; ++i) e.emplace_back(i * n + i, float(1.0 + absSum[size_t(i)]));
+  std::sort(e.begin(), e.end(), [](const auto &a, const auto &b) { return a.first < b.first; });
+  CsrHost A;
+  A.rows = A.cols = n;
+  A.rowPtr.assign(size_t(n + 1), 0);
+  A.colInd.reserve(e.size());
+  A.val.reserve(e.size());
+  for (const auto &kv : e) {
+    A.rowPtr[size_t(kv.first / n + 1)]++;
+    A.colInd.push_back(int32_t(kv.first % n));
+    A.val.push_back(kv.second);
+  }
+  for (int64_t r = 0; r < n; ++r) A.rowPtr[size_t(r + 1)] += A.rowPtr[size_t(r)];
+  return A;
+}
+
 CsrHost read_matrix_market(const std::string &path) {
   std::ifstream f(path);
   TZ_CHECK(f, "cannot open " << path);

@@ -645,6 +645,11 @@ struct CsrHost {
 /// deterministic random band matrix: `nnz` entries with |row - col| < bw, values in [-1,1)
 /// (reference csr_mat.hpp:334-370 uses rand() and all-ones values)
 CsrHost random_band_matrix(int64_t n, int64_t bw, int64_t nnz, uint64_t seed);
+/// symmetric positive definite band matrix: the off-diagonal entries of random_band_matrix(n,
+/// bw, nnz, seed) mirrored across the diagonal (a pair present on both sides keeps the upper
+/// triangle's value) and a_ii = 1 + sum_j |a_ij| (summed in f64, rounded to f32): strictly
+/// diagonally dominant. Rows sorted, no duplicates.
+CsrHost spd_band_matrix(int64_t n, int64_t bw, int64_t nnz, uint64_t seed);
 /// Matrix Market coordinate file -> CSR (real / integer / pattern values; general, symmetric
 /// or skew-symmetric storage; 1-based indices; duplicate entries summed). The reference vendors
 /// an MTX reader (thirdparty/cwpearson/mm) but never calls it; here the SpMV workload can run
@@ -782,6 +787,91 @@ private:
   std::shared_ptr<const Graph> inner_;
   std::shared_ptr<Graph> form_graph(bool accum, const std::string &p);
   OpPtr local_op(bool accum, const std::string &p);
+};
+
+// ------------------------------------------------------------------ conjugate gradient
+
+/// Conjugate gradient on one rank (cg.cpp; not in the reference, whose SpMV workload is the one
+/// product y = A x). One schedule run is one CG iteration on A x = b; the state (x, r, p and
+/// the scalar rr = r . r) lives in device buffers between iterations and between runs. Several
+/// ranks would need a halo of p and an allreduce per dot product: not built.
+struct CgArgs {
+  int64_t m = 150000;
+  int64_t bw = 0;  // 0 = m
+  int64_t nnz = 0; // 0 = 5 m (off-diagonal draws before mirroring, see spd_band_matrix)
+  int64_t nnz_actual = 0; // set by ConjugateGradient: the entries of the matrix it built or read
+  uint64_t seed = 1;
+  // Matrix Market file of a square, symmetric matrix (checked; it should be positive definite)
+  // instead of spd_band_matrix
+  std::string matrix = "";
+  int device = -1;
+  // "plain": one kernel per step (SpMV, dot, alpha, two axpys, dot, beta, xpay: 8 launches);
+  // "fused": SpMV + dot, x update, r update + dot, p update (4 launches, the scalars formed in
+  // the consumers' prologues); "choice": a ChoiceOp over both
+  std::string form = "choice";
+  int lanes = kern::kSpmvIlp + 4; // kern::csr_spmv variant of the plain form's SpMV
+  // "random": b uniform in [-1, 1), derived from seed; "zero": b = 0 (the degenerate system,
+  // which must stay at x = 0 without a NaN)
+  std::string rhs = "random";
+  std::string prefix = "cg_";
+  int rank = 0, size = 1;
+  Json json() const;
+};
+
+class ConjugateGradient : public std::enable_shared_from_this<ConjugateGradient> {
+public:
+  explicit ConjugateGradient(CgArgs a);
+  const CgArgs &args() const { return a_; }
+  const CsrHost &matrix() const { return A_; }
+  int64_t rows() const { return A_.rows; }
+
+  void setup();
+  bool ready() const { return dX_.get() != nullptr; }
+  /// cg_form (ChoiceOp: cg_plain | cg_fused), or the fixed form's compound op
+  void add_to_graph(Graph &g);
+  /// x = 0, r = p = b, rr = b . b (and the rr partials that sum to it); synchronous
+  void reset();
+  std::vector<float> x() const { return down(dX_); }
+  std::vector<float> r() const { return down(dR_); }
+  std::vector<float> p() const { return down(dP_); }
+  const std::vector<float> &b() const { return b_; }
+  /// r . r of the current residual (the sum of the rr partials, in the kernels' order)
+  double rr() const;
+  /// max |x - x_ref| / max |x_ref| against k iterations of CG in f64 on the host (same guards)
+  double check(int k) const;
+
+  // op bodies
+  static constexpr int kFusedLanes = kern::kSpmvIlp + 4;
+  int np_vec() const { return kern::dot_partial_count(rows()); }
+  int np_spmv() const { return kern::spmv_dot_partial_count(int(rows()), kFusedLanes); }
+  double spmv_bytes() const { return 12.0 * double(A_.nnz()) + 8.0 * double(rows()); }
+  void spmv(void *stream) const;      // q = A p
+  void dot_pq(void *stream) const;    // pq partials = p . q
+  void alpha(void *stream) const;     // alpha = rr / pq
+  void update_x(void *stream) const;  // x += alpha p
+  void update_r(void *stream) const;  // r -= alpha q
+  void dot_rr(void *stream) const;    // rr partials = r . r
+  void beta(void *stream) const;      // beta = rr_new / rr; rr = rr_new
+  void update_p(void *stream) const;  // p = r + beta p
+  void fused_spmv_dot(void *stream) const; // q = A p, pq partials; rr = sum of the rr partials
+  void fused_x(void *stream) const;
+  void fused_r(void *stream) const;
+  void fused_p(void *stream) const;
+
+private:
+  std::vector<float> down(const DeviceBuffer &d) const;
+  std::shared_ptr<Graph> form_graph(bool fused) const;
+  CgArgs a_;
+  CsrHost A_;
+  std::vector<float> b_;
+  DeviceBuffer dRow_, dCol_, dVal_, dB_, dX_, dR_, dP_, dQ_;
+  // [pq partials 256 | rr partials 256 | rr | alpha | beta]
+  DeviceBuffer dScal_;
+  double *pq_() const { return dScal_.as<double>(); }
+  double *rrp_() const { return dScal_.as<double>() + kern::kCgMaxPartials; }
+  double *rr_() const { return dScal_.as<double>() + 2 * kern::kCgMaxPartials; }
+  double *alpha_() const { return rr_() + 1; }
+  double *beta_() const { return rr_() + 2; }
 };
 
 /// Horizontal fusion (fused_ops.cpp): the halo's self moves `dirs` and the SpMV's local product

@@ -1,0 +1,45 @@
+"""Conjugate gradient on one rank: one schedule run is one CG iteration on A x = b.
+
+Not in the reference (its SpMV workload is the single product y = A x). A is a symmetric,
+strictly diagonally dominant band matrix (``spd_band_matrix``: m = 150,000 rows, 5 m random
+off-diagonal draws mirrored across the diagonal) or a symmetric Matrix Market file; b is a fixed
+pseudo-random vector. The search chooses between the plain form (8 launches) and the fused form
+(4 launches) and places the x update beside the r -> r.r -> beta -> p chain.
+"""
+from __future__ import annotations
+
+import dataclasses
+
+from .. import _tz
+
+
+@dataclasses.dataclass
+class CgConfig:
+    m: int = 150_000
+    bw: int = 0         # 0 = m
+    nnz: int = 0        # 0 = 5 m (before mirroring)
+    seed: int = 1
+    matrix: str = ""    # symmetric Matrix Market file instead of the band matrix
+    form: str = "choice"  # plain (one kernel per step) | fused (4 launches) | choice
+    lanes: int = _tz.kernels.SPMV_ILP + 4  # csr_spmv variant of the plain form's SpMV
+    rhs: str = "random"  # random: b in [-1, 1) from seed | zero: b = 0 (the degenerate system)
+    prefix: str = "cg_"
+
+    def args(self, rank: int = 0, size: int = 1, device: int = -1) -> "_tz.CgArgs":
+        a = _tz.CgArgs()
+        a.m, a.bw, a.nnz, a.seed = self.m, self.bw, self.nnz, self.seed
+        a.matrix, a.form, a.lanes, a.rhs, a.prefix = self.matrix, self.form, self.lanes, self.rhs, self.prefix
+        a.rank, a.size, a.device = rank, size, device
+        return a
+
+
+def build_cg(cfg: CgConfig, ctrl=None, device: int = -1, setup: bool = True, graph=None):
+    """(ConjugateGradient, Graph). One rank only: a control plane of several ranks raises."""
+    rank = ctrl.rank if ctrl is not None else 0
+    size = ctrl.size if ctrl is not None else 1
+    c = _tz.ConjugateGradient(cfg.args(rank, size, device))
+    if setup:
+        c.setup()
+    g = graph if graph is not None else _tz.Graph()
+    c.add_to_graph(g)
+    return c, g
