@@ -331,6 +331,8 @@ def cmd_run(a) -> int:
         out["cg_check_iters"] = w.cg_check_iters
         out["cg_max_rel_err"] = wl["cg"].check(w.cg_check_iters)
         ok &= out["cg_max_rel_err"] < 1e-4
+        # the true residual ||b - A x|| / ||b|| of that x: the same quantity in every form
+        out["cg_residual"] = wl["cg"].residual()
     rt.precompile(a.warmup)
     rt.run(a.warmup)
     rt.precompile(a.iters)  # the remainder of the unroll as one graph, compiled before timing
@@ -529,9 +531,10 @@ def _parser() -> argparse.ArgumentParser:
                         "rows (root, the reference's setup) or every rank builds it (local)")
     s.add_argument("--cg-m", type=int, default=150_000,
                    help="cg (one rank): rows of the symmetric positive definite band matrix")
-    s.add_argument("--cg-form", default="choice", choices=["choice", "plain", "fused"],
+    s.add_argument("--cg-form", default="choice", choices=["choice", "plain", "fused", "sr", "all"],
                    help="cg: one kernel per step (plain, 8 launches), fused (4 launches) or both "
-                        "as a ChoiceOp")
+                        "as a ChoiceOp (choice); the single-reduction recurrence (sr, 2 launches) "
+                        "or all three as a ChoiceOp (all)")
     s.add_argument("--cg-matrix", default="",
                    help="cg: symmetric Matrix Market file instead of the band matrix")
     s.add_argument("--cg-check-iters", type=int, default=25,

@@ -1,5 +1,6 @@
 // Conjugate-gradient kernels for gfx950: dot products, vector updates whose coefficient lives in
-// device memory, and the fused forms (SpMV + dot, update + dot). Not in the reference.
+// device memory, the fused forms (SpMV + dot, update + dot) and the single-reduction form's two
+// kernels (SpMV + two dots, one update of p, s, x and r). Not in the reference.
 //
 // Vectors are f32; dot products accumulate in f64 (the product of two f32 values is exact in
 // f64); every scalar (rr, alpha, beta) is an f64 in device memory, so no launch argument carries
@@ -243,6 +244,111 @@ __global__ __launch_bounds__(kSpmvThreads) void csr_spmv_dot_k(int nRows, const 
   if (threadIdx.x == 0) partialsPq[blockIdx.x] = s;
 }
 
+// The single-reduction (Chronopoulos-Gear) recurrence: both dot products of an iteration come
+// from the same vectors, gamma = r . r and delta = r . (A r), so both ride on the SpMV.
+//
+// w = A r as csr_spmv_dot_k computes q (same row body, same grid) and the block's partials of
+// gamma and delta. Block 0 also moves the scalars the previous update published into the places
+// the next update reads (gammaOut may be null): this launch lies between their writer and their
+// next reader, and nothing in it reads either side.
+template <int W, int K>
+__global__ __launch_bounds__(kSpmvThreads) void csr_spmv_dot2_k(int nRows, const int32_t *__restrict__ rowPtr,
+                                                                const int32_t *__restrict__ colInd,
+                                                                const float *__restrict__ val,
+                                                                const float *__restrict__ r,
+                                                                float *__restrict__ w,
+                                                                double *__restrict__ partialsGamma,
+                                                                double *__restrict__ partialsDelta,
+                                                                const double *__restrict__ gammaOut,
+                                                                const double *__restrict__ alphaOut,
+                                                                double *__restrict__ gammaPrev,
+                                                                double *__restrict__ alphaPrev) {
+  __shared__ double sh[kSpmvThreads / 64];
+  if (gammaOut && blockIdx.x == 0 && threadIdx.x == 0) {
+    *gammaPrev = *gammaOut;
+    *alphaPrev = *alphaOut;
+  }
+  const int lane = threadIdx.x & (W - 1);
+  const int rowsPerPass = int(gridDim.x) * (kSpmvThreads / W);
+  double accG = 0.0, accD = 0.0;
+  // whole W-lane groups leave the loop together (W divides 64)
+  for (int row = (blockIdx.x * kSpmvThreads + threadIdx.x) / W; row < nRows; row += rowsPerPass) {
+    const float sum = dev::csr_spmv_ilp_sum<W, K>(row, lane, rowPtr, colInd, val, r);
+    if (lane == 0) {
+      const double ri = double(r[row]);
+      w[row] = sum;
+      accG += ri * ri;
+      accD += ri * double(sum);
+    }
+  }
+  const double g = block_sum<kSpmvThreads / 64>(accG, sh);
+  const double d = block_sum<kSpmvThreads / 64>(accD, sh);
+  if (threadIdx.x == 0) {
+    partialsGamma[blockIdx.x] = g;
+    partialsDelta[blockIdx.x] = d;
+  }
+}
+
+// alpha = gamma / (delta - beta * (gamma / alphaPrev)), every division guarded. The product and
+// the difference round separately (no fma), so the bits are those of the same expression in any
+// IEEE f64 arithmetic. This file is built with -ffp-contract=fast, which disregards `#pragma
+// clang fp contract(off)` (the difference still compiled to one v_fma_f64), so the product
+// passes through an empty asm statement that the compiler cannot fuse across.
+__device__ __forceinline__ double sr_alpha(double gamma, double delta, double beta, double alphaPrev) {
+  double t = beta * guarded_div(gamma, alphaPrev);
+  asm volatile("" : "+v"(t));
+  return guarded_div(gamma, delta - t);
+}
+
+// One pass over the five vectors: beta and alpha formed in the prologue from the two slabs and
+// the previous iteration's gamma and alpha, then per element
+//   p = fmaf(b, p, r)   s = fmaf(b, s, w)   x = fmaf(a, p, x)   r = fmaf(-a, s, r)
+// (xpay_pass, xpay_pass, axpy_pass(+a), axpy_pass(-a) in one sweep). Block 0 publishes gamma,
+// alpha and beta to places no block of this launch reads.
+__global__ __launch_bounds__(kThreads) void cg_sr_update_k(int64_t n, const double *__restrict__ partialsGamma,
+                                                           const double *__restrict__ partialsDelta, int np,
+                                                           const double *__restrict__ gammaPrev,
+                                                           const double *__restrict__ alphaPrev,
+                                                           const float *w, float *r, float *p, float *s,
+                                                           float *x, double *__restrict__ gammaOut,
+                                                           double *__restrict__ alphaOut,
+                                                           double *__restrict__ betaOut) {
+  __shared__ double sh[kThreads / 64];
+  const double gamma = sum_partials<kThreads / 64>(partialsGamma, np, sh);
+  const double delta = sum_partials<kThreads / 64>(partialsDelta, np, sh);
+  const double beta = guarded_div(gamma, *gammaPrev);
+  const double alpha = sr_alpha(gamma, delta, beta, *alphaPrev);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    *gammaOut = gamma;
+    *alphaOut = alpha;
+    *betaOut = beta;
+  }
+  const float b = float(beta), a = float(alpha), na = -a;
+  const bool aw = aligned16(w), ar = aligned16(r), ap = aligned16(p), as = aligned16(s), ax = aligned16(x);
+  const int64_t nq = n / 4, stride = int64_t(gridDim.x) * kThreads;
+  for (int64_t k = int64_t(blockIdx.x) * kThreads + threadIdx.x; k < nq; k += stride) {
+    const float4 wv = load_quad(w, k, aw);
+    float4 rv = load_quad(r, k, ar), pv = load_quad(p, k, ap), sv = load_quad(s, k, as), xv = load_quad(x, k, ax);
+    pv.x = fmaf(b, pv.x, rv.x), pv.y = fmaf(b, pv.y, rv.y), pv.z = fmaf(b, pv.z, rv.z), pv.w = fmaf(b, pv.w, rv.w);
+    sv.x = fmaf(b, sv.x, wv.x), sv.y = fmaf(b, sv.y, wv.y), sv.z = fmaf(b, sv.z, wv.z), sv.w = fmaf(b, sv.w, wv.w);
+    xv.x = fmaf(a, pv.x, xv.x), xv.y = fmaf(a, pv.y, xv.y), xv.z = fmaf(a, pv.z, xv.z), xv.w = fmaf(a, pv.w, xv.w);
+    rv.x = fmaf(na, sv.x, rv.x), rv.y = fmaf(na, sv.y, rv.y), rv.z = fmaf(na, sv.z, rv.z), rv.w = fmaf(na, sv.w, rv.w);
+    store_quad(p, k, ap, pv);
+    store_quad(s, k, as, sv);
+    store_quad(x, k, ax, xv);
+    store_quad(r, k, ar, rv);
+  }
+  const int64_t t = nq * 4 + threadIdx.x;
+  if (blockIdx.x == 0 && t < n) {
+    const float rt = r[t];
+    const float pt = fmaf(b, p[t], rt), st = fmaf(b, s[t], w[t]);
+    p[t] = pt;
+    s[t] = st;
+    x[t] = fmaf(a, pt, x[t]);
+    r[t] = fmaf(na, st, rt);
+  }
+}
+
 void check_vec(const char *what, int64_t n, const void *a, const void *b) {
   if (n <= 0) throw std::runtime_error(std::string(what) + ": n must be positive");
   if (!a || !b) throw std::runtime_error(std::string(what) + ": null pointer");
@@ -363,6 +469,49 @@ void csr_spmv_dot(int nRows, const int32_t *rowPtr, const int32_t *colInd, const
   case 2: hipLaunchKernelGGL((csr_spmv_dot_k<2, 8>), g, b, 0, s, nRows, rowPtr, colInd, val, p, q, partialsPq, partialsRr, npRr, rr); break;
   default: hipLaunchKernelGGL((csr_spmv_dot_k<4, 4>), g, b, 0, s, nRows, rowPtr, colInd, val, p, q, partialsPq, partialsRr, npRr, rr); break;
   }
+  TZ_HIP_LAUNCH_CHECK();
+}
+
+void csr_spmv_dot2(int nRows, const int32_t *rowPtr, const int32_t *colInd, const float *val, const float *r,
+                   float *w, int lanes, double *partialsGamma, double *partialsDelta, const double *gammaOut,
+                   const double *alphaOut, double *gammaPrev, double *alphaPrev, void *stream) {
+  if (nRows <= 0) throw std::runtime_error("csr_spmv_dot2: nRows must be positive");
+  if (!rowPtr || !colInd || !val || !r || !w || !partialsGamma || !partialsDelta)
+    throw std::runtime_error("csr_spmv_dot2: null pointer");
+  if (partialsGamma == partialsDelta) throw std::runtime_error("csr_spmv_dot2: the two slabs must differ");
+  if (gammaOut || alphaOut || gammaPrev || alphaPrev) {
+    if (!gammaOut || !alphaOut || !gammaPrev || !alphaPrev)
+      throw std::runtime_error("csr_spmv_dot2: null pointer (the four scalars come together or not at all)");
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int W = lanes - kSpmvIlp;
+  if (W != 1 && W != 2 && W != 4) throw std::runtime_error("csr_spmv_dot2: lanes must be kSpmvIlp + 1, 2 or 4");
+  const dim3 g(unsigned(spmv_dot_partial_count(nRows, W))), b(kSpmvThreads);
+  switch (W) {
+  case 1: hipLaunchKernelGGL((csr_spmv_dot2_k<1, 16>), g, b, 0, s, nRows, rowPtr, colInd, val, r, w, partialsGamma, partialsDelta, gammaOut, alphaOut, gammaPrev, alphaPrev); break;
+  case 2: hipLaunchKernelGGL((csr_spmv_dot2_k<2, 8>), g, b, 0, s, nRows, rowPtr, colInd, val, r, w, partialsGamma, partialsDelta, gammaOut, alphaOut, gammaPrev, alphaPrev); break;
+  default: hipLaunchKernelGGL((csr_spmv_dot2_k<4, 4>), g, b, 0, s, nRows, rowPtr, colInd, val, r, w, partialsGamma, partialsDelta, gammaOut, alphaOut, gammaPrev, alphaPrev); break;
+  }
+  TZ_HIP_LAUNCH_CHECK();
+}
+
+void cg_sr_update(int64_t n, const double *partialsGamma, const double *partialsDelta, int np,
+                  const double *gammaPrev, const double *alphaPrev, const float *w, float *r, float *p, float *s,
+                  float *x, double *gammaOut, double *alphaOut, double *betaOut, void *stream) {
+  check_vec("cg_sr_update", n, w, r);
+  check_vec("cg_sr_update", n, p, s);
+  check_vec("cg_sr_update", n, x, x);
+  check_np("cg_sr_update", partialsGamma, np);
+  check_np("cg_sr_update", partialsDelta, np);
+  if (!gammaPrev || !alphaPrev || !gammaOut || !alphaOut || !betaOut)
+    throw std::runtime_error("cg_sr_update: null pointer");
+  // a block reads gammaPrev / alphaPrev while block 0 may already have published
+  if (gammaOut == gammaPrev || gammaOut == alphaPrev || alphaOut == gammaPrev || alphaOut == alphaPrev ||
+      betaOut == gammaPrev || betaOut == alphaPrev)
+    throw std::runtime_error("cg_sr_update: the published scalars must not alias the previous ones");
+  hipLaunchKernelGGL(cg_sr_update_k, dim3(dot_partial_count(n)), dim3(kThreads), 0,
+                     static_cast<hipStream_t>(stream), n, partialsGamma, partialsDelta, np, gammaPrev, alphaPrev,
+                     w, r, p, s, x, gammaOut, alphaOut, betaOut);
   TZ_HIP_LAUNCH_CHECK();
 }
 

@@ -261,6 +261,23 @@ void cg_fused_r(int64_t n, const double *partials_pq, int np, const double *rr, 
 /// p = r + beta p with beta = rr != 0 ? sum(partials_rr) / rr : 0 (rr is not written)
 void cg_fused_p(int64_t n, const double *partials_rr, int np, const double *rr, const float *r, float *p,
                 void *stream);
+/// The single-reduction (Chronopoulos-Gear) recurrence, first launch: w = A r as csr_spmv's ILP
+/// kernel computes it (lanes = kSpmvIlp + W, same bits), partials_gamma[b] = block b's share of
+/// r . r and partials_delta[b] of r . w, b < spmv_dot_partial_count(nRows, lanes). With the four
+/// scalar pointers (all or none), block 0 also copies *gamma_out to *gamma_prev and *alpha_out to
+/// *alpha_prev: what the previous cg_sr_update published becomes what the next one reads.
+void csr_spmv_dot2(int nRows, const int32_t *rowPtr, const int32_t *colInd, const float *val, const float *r,
+                   float *w, int lanes, double *partials_gamma, double *partials_delta, const double *gamma_out,
+                   const double *alpha_out, double *gamma_prev, double *alpha_prev, void *stream);
+/// Second launch. With gamma and delta the sums of the two slabs and gdiv(a, b) = b != 0 ? a / b : 0:
+///   beta = gdiv(gamma, *gamma_prev), alpha = gdiv(gamma, delta - beta * gdiv(gamma, *alpha_prev))
+/// (the product and the difference round separately), then with both rounded to f32
+///   p = fmaf(beta, p, r), s = fmaf(beta, s, w), x = fmaf(alpha, p, x), r = fmaf(-alpha, s, r)
+/// (same bits as xpay_dev_f32 twice and axpy_dev_f32 twice). Block 0 stores gamma, alpha and beta
+/// to the three outputs, which must not alias gamma_prev / alpha_prev; those are not written.
+void cg_sr_update(int64_t n, const double *partials_gamma, const double *partials_delta, int np,
+                  const double *gamma_prev, const double *alpha_prev, const float *w, float *r, float *p, float *s,
+                  float *x, double *gamma_out, double *alpha_out, double *beta_out, void *stream);
 
 /// y += alpha * x (f64)
 void axpy_f64(int64_t n, double alpha, const double *x, double *y, void *stream);

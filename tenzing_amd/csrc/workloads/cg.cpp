@@ -12,6 +12,11 @@
 //   fused: pq slab <- spmvdot, rr slab <- the r update, rr <- block 0 of the next iteration's
 //          spmvdot (after the last reader of the old rr, the p update, and before the first
 //          reader of the new one); alpha and beta live in registers only
+//   sr:    the single-reduction (Chronopoulos-Gear) recurrence, two launches. gamma slab (the rr
+//          slab's place) and delta slab (the pq slab's) <- spmvdot; gamma, alpha, beta <- block 0
+//          of the update, which no block of that launch reads; gamma_prev, alpha_prev <- block 0
+//          of the next iteration's spmvdot, which copies them from gamma and alpha (after their
+//          last reader, the update, and before the next one)
 #include "workloads.hpp"
 
 #include "core/util.hpp"
@@ -92,8 +97,8 @@ ConjugateGradient::ConjugateGradient(CgArgs a) : a_(std::move(a)) {
   TZ_CHECK(a_.size == 1 && a_.rank == 0,
            "the conjugate-gradient workload runs on one rank only (got rank " << a_.rank << " of " << a_.size
                << "): several ranks need a halo of p and an allreduce per dot product");
-  TZ_CHECK(a_.form == "choice" || a_.form == "plain" || a_.form == "fused",
-           "CG form must be choice, plain or fused (got " << a_.form << ")");
+  TZ_CHECK(a_.form == "choice" || a_.form == "plain" || a_.form == "fused" || a_.form == "sr" || a_.form == "all",
+           "CG form must be choice, plain, fused, sr or all (got " << a_.form << ")");
   TZ_CHECK(a_.rhs == "random" || a_.rhs == "zero", "CG rhs must be random or zero (got " << a_.rhs << ")");
   if (!a_.matrix.empty()) {
     A_ = read_matrix_market(a_.matrix);
@@ -146,7 +151,9 @@ void ConjugateGradient::setup() {
   dR_ = DeviceBuffer(vb);
   dP_ = DeviceBuffer(vb);
   dQ_ = DeviceBuffer(vb);
-  dScal_ = DeviceBuffer((2 * size_t(kern::kCgMaxPartials) + 3) * sizeof(double));
+  dS_ = DeviceBuffer(vb);
+  dW_ = DeviceBuffer(vb);
+  dScal_ = DeviceBuffer((3 * size_t(kern::kCgMaxPartials) + 8) * sizeof(double));
   dX_ = DeviceBuffer(vb);
   reset();
 }
@@ -158,6 +165,8 @@ void ConjugateGradient::reset() {
   const size_t vb = size_t(rows()) * 4;
   TZ_HIP(hipMemset(dX_.get(), 0, dX_.bytes()));
   TZ_HIP(hipMemset(dQ_.get(), 0, dQ_.bytes()));
+  TZ_HIP(hipMemset(dS_.get(), 0, dS_.bytes()));
+  TZ_HIP(hipMemset(dW_.get(), 0, dW_.bytes()));
   TZ_HIP(hipMemset(dScal_.get(), 0, dScal_.bytes()));
   TZ_HIP(hipMemcpy(dR_.get(), dB_.get(), vb, hipMemcpyDeviceToDevice));
   TZ_HIP(hipMemcpy(dP_.get(), dB_.get(), vb, hipMemcpyDeviceToDevice));
@@ -177,9 +186,27 @@ std::vector<float> ConjugateGradient::down(const DeviceBuffer &d) const {
 double ConjugateGradient::rr() const {
   TZ_CHECK(ready(), "CG not set up");
   TZ_HIP(hipDeviceSynchronize());
+  // from r itself: the single-reduction form's slabs hold the previous r's products. The layout
+  // is dot_rr's and the fused r update's, so for those forms these are the bits of the rr slab.
+  kern::dot_partials_f32(rows(), dR_.as<float>(), dR_.as<float>(), scratch_(), nullptr);
+  TZ_HIP(hipDeviceSynchronize());
   std::vector<double> part(static_cast<size_t>(kern::kCgMaxPartials), 0.0);
-  TZ_HIP(hipMemcpy(part.data(), rrp_(), part.size() * sizeof(double), hipMemcpyDeviceToHost));
+  TZ_HIP(hipMemcpy(part.data(), scratch_(), size_t(np_vec()) * sizeof(double), hipMemcpyDeviceToHost));
   return sum_partials_host(part.data(), np_vec());
+}
+
+double ConjugateGradient::residual() const {
+  const std::vector<float> xd = this->x();
+  double res = 0, bb = 0;
+  for (size_t i = 0; i < size_t(rows()); ++i) {
+    double s = 0;
+    for (int32_t j = A_.rowPtr[i]; j < A_.rowPtr[i + 1]; ++j)
+      s += double(A_.val[size_t(j)]) * double(xd[size_t(A_.colInd[size_t(j)])]);
+    const double d = double(b_[i]) - s;
+    res += d * d;
+    bb += double(b_[i]) * double(b_[i]);
+  }
+  return bb > 0 ? std::sqrt(res / bb) : std::sqrt(res);
 }
 
 double ConjugateGradient::check(int k) const {
@@ -253,7 +280,34 @@ void ConjugateGradient::fused_p(void *s) const {
   kern::cg_fused_p(rows(), rrp_(), np_vec(), rr_(), dR_.as<float>(), dP_.as<float>(), s);
 }
 
+void ConjugateGradient::sr_spmv_dot(void *s) const {
+  kern::csr_spmv_dot2(int(rows()), dRow_.as<int32_t>(), dCol_.as<int32_t>(), dVal_.as<float>(), dR_.as<float>(),
+                      dW_.as<float>(), kFusedLanes, rrp_(), pq_(), srGamma_(), srAlpha_(), srGammaPrev_(),
+                      srAlphaPrev_(), s);
+}
+void ConjugateGradient::sr_update(void *s) const {
+  kern::cg_sr_update(rows(), rrp_(), pq_(), np_spmv(), srGammaPrev_(), srAlphaPrev_(), dW_.as<float>(),
+                     dR_.as<float>(), dP_.as<float>(), dS_.as<float>(), dX_.as<float>(), srGamma_(), srAlpha_(),
+                     srBeta_(), s);
+}
+
 // ------------------------------------------------------------------ graph
+
+std::shared_ptr<Graph> ConjugateGradient::sr_graph() const {
+  auto self = shared_from_this();
+  const std::string p = a_.prefix + "s_";
+  // cost model as in form_graph: the SpMV with two dots is the fused form's, the update one
+  // launch with a two-slab prologue over 36 bytes per row (reads w, r, p, s, x; writes r, p, s, x)
+  auto sd = std::make_shared<CgOp>(self, p + "spmvdot", "CgSpmvDot2", &ConjugateGradient::sr_spmv_dot, 4.5,
+                                   spmv_bytes(), 3.0e6);
+  auto up = std::make_shared<CgOp>(self, p + "update", "CgSrUpdate", &ConjugateGradient::sr_update, 3.5,
+                                   36.0 * double(rows()), 4.0e6);
+  auto g = std::make_shared<Graph>();
+  g->start_then(sd);
+  g->then(sd, up); // w, both slabs, gamma_prev and alpha_prev
+  g->then_finish(up);
+  return g;
+}
 
 std::shared_ptr<Graph> ConjugateGradient::form_graph(bool fused) const {
   auto self = shared_from_this();
@@ -304,10 +358,13 @@ std::shared_ptr<Graph> ConjugateGradient::form_graph(bool fused) const {
 void ConjugateGradient::add_to_graph(Graph &g) {
   const std::string &p = a_.prefix;
   OpPtr top;
-  if (a_.form == "choice") {
+  if (a_.form == "choice" || a_.form == "all") {
     std::vector<OpPtr> alts = {std::make_shared<StaticCompoundOp>(p + "plain", form_graph(false)),
                                std::make_shared<StaticCompoundOp>(p + "fused", form_graph(true))};
+    if (a_.form == "all") alts.push_back(std::make_shared<StaticCompoundOp>(p + "sr", sr_graph()));
     top = std::make_shared<StaticChoiceOp>(p + "form", alts);
+  } else if (a_.form == "sr") {
+    top = std::make_shared<StaticCompoundOp>(p + "sr", sr_graph());
   } else {
     top = std::make_shared<StaticCompoundOp>(p + a_.form, form_graph(a_.form == "fused"));
   }

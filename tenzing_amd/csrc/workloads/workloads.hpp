@@ -793,8 +793,9 @@ private:
 
 /// Conjugate gradient on one rank (cg.cpp; not in the reference, whose SpMV workload is the one
 /// product y = A x). One schedule run is one CG iteration on A x = b; the state (x, r, p and
-/// the scalar rr = r . r) lives in device buffers between iterations and between runs. Several
-/// ranks would need a halo of p and an allreduce per dot product: not built.
+/// the scalar rr = r . r; in the single-reduction form also s and two scalars) lives in device
+/// buffers between iterations and between runs. Several ranks would need a halo of p and an
+/// allreduce per dot product: not built.
 struct CgArgs {
   int64_t m = 150000;
   int64_t bw = 0;  // 0 = m
@@ -807,7 +808,9 @@ struct CgArgs {
   int device = -1;
   // "plain": one kernel per step (SpMV, dot, alpha, two axpys, dot, beta, xpay: 8 launches);
   // "fused": SpMV + dot, x update, r update + dot, p update (4 launches, the scalars formed in
-  // the consumers' prologues); "choice": a ChoiceOp over both
+  // the consumers' prologues); "choice": a ChoiceOp over both; "sr": the single-reduction
+  // (Chronopoulos-Gear) recurrence, SpMV + both dots, then one update of p, s, x and r (2
+  // launches); "all": a ChoiceOp over the three
   std::string form = "choice";
   int lanes = kern::kSpmvIlp + 4; // kern::csr_spmv variant of the plain form's SpMV
   // "random": b uniform in [-1, 1), derived from seed; "zero": b = 0 (the degenerate system,
@@ -827,18 +830,25 @@ public:
 
   void setup();
   bool ready() const { return dX_.get() != nullptr; }
-  /// cg_form (ChoiceOp: cg_plain | cg_fused), or the fixed form's compound op
+  /// cg_form (ChoiceOp: cg_plain | cg_fused, with form "all" also | cg_sr), or the fixed form's
+  /// compound op
   void add_to_graph(Graph &g);
-  /// x = 0, r = p = b, rr = b . b (and the rr partials that sum to it); synchronous
+  /// x = 0, r = p = b, rr = b . b (and the rr partials that sum to it), s = 0 and the
+  /// single-reduction form's scalars 0 (its first iteration then has beta = 0); synchronous
   void reset();
   std::vector<float> x() const { return down(dX_); }
   std::vector<float> r() const { return down(dR_); }
   std::vector<float> p() const { return down(dP_); }
   const std::vector<float> &b() const { return b_; }
-  /// r . r of the current residual (the sum of the rr partials, in the kernels' order)
+  /// r . r of the current r in every form: its partials as dot_partials_f32 writes them (the
+  /// bits of the plain and fused forms' rr slab), summed in the kernels' order
   double rr() const;
   /// max |x - x_ref| / max |x_ref| against k iterations of CG in f64 on the host (same guards)
   double check(int k) const;
+  /// the true residual ||b - A x||_2 / ||b||_2 of the current x, in f64 on the host (0 for b = 0).
+  /// The single-reduction form's r is a recurrence of its own, so rr() no longer is this quantity
+  /// by construction; this one compares the forms.
+  double residual() const;
 
   // op bodies
   static constexpr int kFusedLanes = kern::kSpmvIlp + 4;
@@ -857,21 +867,33 @@ public:
   void fused_x(void *stream) const;
   void fused_r(void *stream) const;
   void fused_p(void *stream) const;
+  void sr_spmv_dot(void *stream) const; // w = A r, gamma and delta partials; the scalars move on
+  void sr_update(void *stream) const;   // beta, alpha; p, s, x, r
 
 private:
   std::vector<float> down(const DeviceBuffer &d) const;
   std::shared_ptr<Graph> form_graph(bool fused) const;
+  std::shared_ptr<Graph> sr_graph() const;
   CgArgs a_;
   CsrHost A_;
   std::vector<float> b_;
   DeviceBuffer dRow_, dCol_, dVal_, dB_, dX_, dR_, dP_, dQ_;
-  // [pq partials 256 | rr partials 256 | rr | alpha | beta]
+  DeviceBuffer dS_, dW_; // the single-reduction form: s = A p by recurrence, w = A r
+  // [pq partials 256 | rr partials 256 | rr | alpha | beta | the single-reduction form's gamma,
+  //  alpha, beta, gamma_prev, alpha_prev | rr()'s scratch partials 256]; that form's delta slab
+  // is the pq slab and its gamma slab the rr slab
   DeviceBuffer dScal_;
   double *pq_() const { return dScal_.as<double>(); }
   double *rrp_() const { return dScal_.as<double>() + kern::kCgMaxPartials; }
   double *rr_() const { return dScal_.as<double>() + 2 * kern::kCgMaxPartials; }
   double *alpha_() const { return rr_() + 1; }
   double *beta_() const { return rr_() + 2; }
+  double *srGamma_() const { return rr_() + 3; }
+  double *srAlpha_() const { return rr_() + 4; }
+  double *srBeta_() const { return rr_() + 5; }
+  double *srGammaPrev_() const { return rr_() + 6; }
+  double *srAlphaPrev_() const { return rr_() + 7; }
+  double *scratch_() const { return rr_() + 8; }
 };
 
 /// Horizontal fusion (fused_ops.cpp): the halo's self moves `dirs` and the SpMV's local product

@@ -4,7 +4,9 @@ Not in the reference (its SpMV workload is the single product y = A x). A is a s
 strictly diagonally dominant band matrix (``spd_band_matrix``: m = 150,000 rows, 5 m random
 off-diagonal draws mirrored across the diagonal) or a symmetric Matrix Market file; b is a fixed
 pseudo-random vector. The search chooses between the plain form (8 launches) and the fused form
-(4 launches) and places the x update beside the r -> r.r -> beta -> p chain.
+(4 launches) and places the x update beside the r -> r.r -> beta -> p chain. ``form="sr"`` is
+the single-reduction (Chronopoulos-Gear) recurrence in 2 launches: an SpMV of r that also forms
+r.r and r.(A r), then one update of p, s, x and r; ``form="all"`` offers all three to the search.
 """
 from __future__ import annotations
 
@@ -20,7 +22,9 @@ class CgConfig:
     nnz: int = 0        # 0 = 5 m (before mirroring)
     seed: int = 1
     matrix: str = ""    # symmetric Matrix Market file instead of the band matrix
-    form: str = "choice"  # plain (one kernel per step) | fused (4 launches) | choice
+    # plain (one kernel per step) | fused (4 launches) | choice (plain | fused) |
+    # sr (single reduction, 2 launches) | all (plain | fused | sr)
+    form: str = "choice"
     lanes: int = _tz.kernels.SPMV_ILP + 4  # csr_spmv variant of the plain form's SpMV
     rhs: str = "random"  # random: b in [-1, 1) from seed | zero: b = 0 (the degenerate system)
     prefix: str = "cg_"
