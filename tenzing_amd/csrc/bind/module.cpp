@@ -1484,4 +1484,124 @@ PYBIND11_MODULE(_tz, m) {
   }, py::arg("dst"), py::arg("src"), py::arg("bytes"), py::arg("stream") = 0);
   k.def("busy_wait", [](int64_t t, int b, uintptr_t s) { kern::busy_wait(t, b, P(s)); },
         py::arg("ticks"), py::arg("blocks") = 1, py::arg("stream") = 0);
+  // ---- test support: the signalling puts, their counters and the grid checkers on caller-owned
+  // memory (one process, one device; flags and counters are plain device tensors)
+  auto move_signal = [](uintptr_t done, const std::vector<uintptr_t> &flags, uintptr_t count, uint64_t mask,
+                        int maxBlocks) {
+    TZ_CHECK(int(flags.size()) <= kern::kMaxBoxes, "too many flags");
+    kern::MoveSignal sig;
+    sig.done = reinterpret_cast<unsigned int *>(done);
+    for (size_t i = 0; i < flags.size(); ++i) sig.flag[i] = reinterpret_cast<unsigned long long *>(flags[i]);
+    sig.count = reinterpret_cast<unsigned long long *>(count);
+    sig.store_mask = mask;
+    sig.max_blocks = maxBlocks;
+    return sig;
+  };
+  k.def("box_move_many_signal", [moves_from, move_signal](std::vector<py::dict> ds, uintptr_t done,
+                                                          std::vector<uintptr_t> flags, int maxBlocks,
+                                                          uintptr_t s, uintptr_t count, uint64_t mask) {
+    const std::vector<kern::MoveDesc> ms = moves_from(ds);
+    TZ_CHECK(flags.size() == ms.size(), "one flag per move");
+    kern::box_move_many_signal(ms.data(), int(ms.size()), move_signal(done, flags, count, mask, maxBlocks), P(s));
+  }, py::arg("moves"), py::arg("done"), py::arg("flags"), py::arg("max_blocks") = 0, py::arg("stream") = 0,
+     py::arg("count") = 0, py::arg("store_mask") = 0,
+     "peer-put moves: flags[i] += 1 once box i is stored; done: one zeroed u32 per box (store_mask must be 0)");
+  k.def("box_pack_many_signal", [move_signal](uintptr_t grid, std::vector<py::dict> ds, uintptr_t done,
+                                              std::vector<uintptr_t> flags, uintptr_t count, uint64_t mask,
+                                              int maxBlocks, uintptr_t s) {
+    std::vector<kern::BoxDesc> bs;
+    for (auto &d : ds) bs.push_back(box_from_dict(d));
+    TZ_CHECK(flags.size() == bs.size(), "one flag per box");
+    kern::box_pack_many_signal(reinterpret_cast<double *>(grid), bs.data(), int(bs.size()),
+                               move_signal(done, flags, count, mask, maxBlocks), P(s));
+  }, py::arg("grid"), py::arg("boxes"), py::arg("done"), py::arg("flags"), py::arg("count") = 0,
+     py::arg("store_mask") = 0, py::arg("max_blocks") = 0, py::arg("stream") = 0,
+     "peer-put packs; boxes in store_mask store ++count[i] into flags[i] instead of adding 1");
+  auto counters = [](const std::vector<uintptr_t> &v) {
+    std::vector<unsigned long long *> out;
+    for (uintptr_t p : v) out.push_back(reinterpret_cast<unsigned long long *>(p));
+    return out;
+  };
+  k.def("ipc_signal", [counters](std::vector<uintptr_t> sig, uintptr_t count, uintptr_t s) {
+    const auto v = counters(sig);
+    kern::ipc_signal(v.data(), int(v.size()), P(s), reinterpret_cast<unsigned long long *>(count));
+  }, py::arg("counters"), py::arg("count") = 0, py::arg("stream") = 0,
+     "counters[k] += 1 (system scope); with count (device u64 array): counters[k] = ++count[k]");
+  k.def("ipc_wait", [counters](uintptr_t arrive, uintptr_t expected, std::vector<int> slots, uintptr_t err,
+                               double timeoutS, int lag, py::object signal, uintptr_t s) {
+    std::vector<unsigned long long *> v;
+    if (!signal.is_none()) {
+      v = counters(signal.cast<std::vector<uintptr_t>>());
+      TZ_CHECK(v.size() == slots.size(), "one signal counter (or 0) per slot");
+    }
+    kern::ipc_wait(reinterpret_cast<const unsigned long long *>(arrive),
+                   reinterpret_cast<unsigned long long *>(expected), slots.data(), int(slots.size()),
+                   reinterpret_cast<int *>(err), timeoutS, P(s), lag, v.empty() ? nullptr : v.data());
+  }, py::arg("arrive"), py::arg("expected"), py::arg("slots"), py::arg("err"), py::arg("timeout_s"),
+     py::arg("lag") = 0, py::arg("signal") = py::none(), py::arg("stream") = 0,
+     "wait until arrive[s] >= expected[s] + 1 - lag for every slot s, then expected[s] += 1 and signal[k] += 1");
+  k.def("gather_put_signal", [](uintptr_t src, uintptr_t idx, std::vector<py::dict> segs, uintptr_t done,
+                                uintptr_t s) {
+    std::vector<kern::PutSeg> ps;
+    for (auto &d : segs) {
+      kern::PutSeg p;
+      p.dst = reinterpret_cast<float *>(d["dst"].cast<uintptr_t>());
+      p.off = d["off"].cast<int32_t>();
+      p.n = d["n"].cast<int32_t>();
+      p.flag = reinterpret_cast<unsigned long long *>(d["flag"].cast<uintptr_t>());
+      ps.push_back(p);
+    }
+    kern::gather_put_signal(reinterpret_cast<const float *>(src), reinterpret_cast<const int32_t *>(idx),
+                            ps.data(), int(ps.size()), reinterpret_cast<unsigned int *>(done), P(s));
+  }, py::arg("src"), py::arg("idx"), py::arg("segs"), py::arg("done"), py::arg("stream") = 0,
+     "segs: dicts dst, off, n, flag: dst[i] = src[idx[off + i]], then flag += 1; done: one zeroed u32 per segment");
+  k.def("copy_many", [](std::vector<py::dict> cs, uintptr_t s) {
+    std::vector<kern::CopyDesc> v;
+    for (auto &c : cs) {
+      kern::CopyDesc d;
+      d.dst = P(c["dst"].cast<uintptr_t>());
+      d.src = P(c["src"].cast<uintptr_t>());
+      d.bytes = c["bytes"].cast<size_t>();
+      v.push_back(d);
+    }
+    kern::copy_many(v.data(), int(v.size()), P(s));
+  }, py::arg("copies"), py::arg("stream") = 0, "copies: dicts dst, src, bytes, all in one launch");
+  // the checkers with a HaloExchange's geometry (no setup() needed), any generation, caller's memory
+  auto geom_of = [](const HaloExchange &h, int gen) {
+    TZ_CHECK(gen >= 0 && gen <= 3, "grid generation must be 0..3 (got " << gen << ")");
+    kern::HaloGeom g = h.geom();
+    g.gen = gen;
+    return g;
+  };
+  auto counted = [](uintptr_t s, const std::function<void(unsigned long long *)> &launch) {
+    hipStream_t st = static_cast<hipStream_t>(P(s));
+    DeviceBuffer c(sizeof(unsigned long long));
+    TZ_HIP(hipMemsetAsync(c.get(), 0, sizeof(unsigned long long), st));
+    launch(c.as<unsigned long long>());
+    unsigned long long n = 0;
+    TZ_HIP(hipMemcpyAsync(&n, c.get(), sizeof(n), hipMemcpyDeviceToHost, st));
+    TZ_HIP(hipStreamSynchronize(st));
+    return uint64_t(n);
+  };
+  k.def("halo_init", [geom_of](const HaloExchange &h, int gen, uintptr_t grid, uintptr_t s) {
+    TZ_CHECK(grid, "halo_init: null grid");
+    kern::halo_init(reinterpret_cast<double *>(grid), geom_of(h, gen), P(s));
+  }, py::arg("halo"), py::arg("gen"), py::arg("grid"), py::arg("stream") = 0,
+     "interior = encoded global coordinate + gen * 2^51, ghosts = -1, over grid_elems() doubles at grid");
+  k.def("halo_check", [geom_of, counted](const HaloExchange &h, int gen, uintptr_t grid, uintptr_t s) {
+    TZ_CHECK(grid, "halo_check: null grid");
+    const kern::HaloGeom g = geom_of(h, gen);
+    return counted(s, [&](unsigned long long *c) {
+      kern::halo_check(reinterpret_cast<const double *>(grid), g, c, P(s));
+    });
+  }, py::arg("halo"), py::arg("gen"), py::arg("grid"), py::arg("stream") = 0,
+     "logical elements of grid that differ from a completed exchange of generation gen (synchronous)");
+  k.def("stencil_check", [geom_of, counted](const HaloExchange &h, int gen, uintptr_t out, uintptr_t s) {
+    TZ_CHECK(out, "stencil_check: null output");
+    const kern::HaloGeom g = geom_of(h, gen);
+    return counted(s, [&](unsigned long long *c) {
+      kern::stencil_check(reinterpret_cast<const double *>(out), g, c, P(s));
+    });
+  }, py::arg("halo"), py::arg("gen"), py::arg("out"), py::arg("stream") = 0,
+     "interior cells of out beyond 2^-49 * want of the 7-point stencil of generation gen (synchronous)");
 }

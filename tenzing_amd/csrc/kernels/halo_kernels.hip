@@ -695,7 +695,17 @@ __global__ __launch_bounds__(kThreads) void halo_check_k(const double *__restric
 }
 
 // stencil mode: out must hold c0 * v + c1 * (6 face neighbours of v) of the initialized field v
-// (global coordinates, periodic), for every interior cell; counts the cells that do not
+// (global coordinates, periodic), for every interior cell; counts the cells that do not.
+// Tolerance: |out - want| <= 2^-49 * want. Every term of the stencil is non-negative (nothing
+// cancels), so any evaluation order of its 7 terms (2 products, 5 sums, 1 product, 1 sum) is
+// within about 5 * 2^-53 * want of the exact value; `want` here and `out` each carry that, and
+// 16 * 2^-53 = 2^-49 bounds their difference (two honest orders in numpy differ by at most
+// 2.5 * 2^-53 * want over 20^3 x 3 cells, generations 0-3). No absolute term: halo_value puts
+// the generation in bits 51-52, so at generation 3 want reaches 7.3e15 and a relative 1e-12 let
+// a stencil that read one y neighbour from the wrong row (off by c1 * 65536) pass. This bound
+// sees a wrong y or z neighbour at every generation. A wrong x neighbour (off by c1 * 1) is
+// below one ulp of `out` at generations 1-3 (ulp(2^51) = 0.5), so no tolerance can see it
+// there; it is seen where want is small: generation 0, q = 0.
 __global__ __launch_bounds__(kThreads) void stencil_check_k(const double *__restrict__ out, HaloGeom g,
                                                             double c0, double c1,
                                                             unsigned long long *count) {
@@ -720,7 +730,7 @@ __global__ __launch_bounds__(kThreads) void stencil_check_k(const double *__rest
     };
     const double want = c0 * v(0, 0, 0) + c1 * (v(-1, 0, 0) + v(1, 0, 0) + v(0, -1, 0) +
                                                 v(0, 1, 0) + v(0, 0, -1) + v(0, 0, 1));
-    bad += fabs(out[idx] - want) > 1e-12 * fabs(want) + 1e-9;
+    bad += !(fabs(out[idx] - want) <= 0x1p-49 * want); // (a NaN counts)
   }
   for (int off = 32; off > 0; off >>= 1) bad += __shfl_xor(bad, off);
   if ((threadIdx.x & 63) == 0 && bad) atomicAdd(count, bad);
@@ -890,6 +900,7 @@ void box_move_many_signal(const MoveDesc *moves, int n, const MoveSignal &sig, v
   if (n <= 0) return;
   if (n > kMaxBoxes) throw std::runtime_error("box_move_many_signal: too many boxes");
   if (!sig.done) throw std::runtime_error("box_move_many_signal: null block counters");
+  if (sig.store_mask) throw std::runtime_error("box_move_many_signal: store mode is for packs only");
   uint32_t total = 0;
   std::vector<int> keep;
   for (int i = 0; i < n; ++i)

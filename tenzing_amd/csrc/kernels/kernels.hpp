@@ -138,6 +138,8 @@ struct MoveSignal {
   /// AtomicOps): box k's flag has one writer, this one, so instead of adding 1 it stores
   /// ++count[k] (count: device memory, one counter per box, owned by the caller) with a
   /// system-scope release store. Boxes not in `store_mask` add 1 as usual.
+  /// box_pack_many_signal only: no move puts into host memory, so box_move_many_signal throws
+  /// when store_mask != 0 (and never reads count) instead of carrying an unused path.
   unsigned long long *count = nullptr;
   uint64_t store_mask = 0;
   /// workgroups per box at most (0: BoxTuning::put_max_blocks)
@@ -351,7 +353,8 @@ void halo_init(double *grid, const HaloGeom &g, void *stream);
 /// count elements that differ from what a completed exchange must leave; result in *count
 void halo_check(const double *grid, const HaloGeom &g, unsigned long long *count, void *stream);
 /// stencil mode: count interior cells of `out` that differ from the 7-point stencil (default
-/// coefficients) of the field halo_init writes (global coordinates, periodic)
+/// coefficients) of the field halo_init writes (global coordinates, periodic) by more than
+/// 2^-49 * want (derivation at stencil_check_k; a NaN counts)
 void stencil_check(const double *out, const HaloGeom &g, unsigned long long *count, void *stream);
 
 } // namespace kern
