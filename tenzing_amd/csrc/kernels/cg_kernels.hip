@@ -21,6 +21,7 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels.hpp"
+#include "launch.hpp"
 #include "spmv_device.hpp"
 
 #include <algorithm>
@@ -32,14 +33,7 @@ namespace kern {
 
 namespace {
 
-#define TZ_HIP_LAUNCH_CHECK()                                                                      \
-  do {                                                                                             \
-    hipError_t e_ = hipGetLastError();                                                             \
-    if (e_ != hipSuccess)                                                                          \
-      throw std::runtime_error(std::string("kernel launch failed: ") + hipGetErrorString(e_));     \
-  } while (0)
-
-constexpr int kThreads = 256;      // vector and scalar kernels
+// the vector and scalar kernels run kThreads (batch_device.hpp) threads per block
 constexpr int kSpmvThreads = 1024; // csr_spmv_dot: at most 256 blocks must cover the chip
 
 // Sum of one value per thread, returned to every thread: xor butterfly inside each wave64 (all
@@ -461,14 +455,12 @@ void csr_spmv_dot(int nRows, const int32_t *rowPtr, const int32_t *colInd, const
     if (!rr) throw std::runtime_error("csr_spmv_dot: null pointer");
   }
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int W = lanes - kSpmvIlp;
-  if (W != 1 && W != 2 && W != 4) throw std::runtime_error("csr_spmv_dot: lanes must be kSpmvIlp + 1, 2 or 4");
-  const dim3 g(unsigned(spmv_dot_partial_count(nRows, W))), b(kSpmvThreads);
-  switch (W) {
-  case 1: hipLaunchKernelGGL((csr_spmv_dot_k<1, 16>), g, b, 0, s, nRows, rowPtr, colInd, val, p, q, partialsPq, partialsRr, npRr, rr); break;
-  case 2: hipLaunchKernelGGL((csr_spmv_dot_k<2, 8>), g, b, 0, s, nRows, rowPtr, colInd, val, p, q, partialsPq, partialsRr, npRr, rr); break;
-  default: hipLaunchKernelGGL((csr_spmv_dot_k<4, 4>), g, b, 0, s, nRows, rowPtr, colInd, val, p, q, partialsPq, partialsRr, npRr, rr); break;
-  }
+  dispatch_ilp(lanes, "csr_spmv_dot: lanes must be kSpmvIlp + 1, 2 or 4", [&](auto w, auto k) {
+    constexpr int W = decltype(w)::value, K = decltype(k)::value;
+    const dim3 g(unsigned(spmv_dot_partial_count(nRows, W))), b(kSpmvThreads);
+    hipLaunchKernelGGL((csr_spmv_dot_k<W, K>), g, b, 0, s, nRows, rowPtr, colInd, val, p, q, partialsPq,
+                       partialsRr, npRr, rr);
+  });
   TZ_HIP_LAUNCH_CHECK();
 }
 
@@ -484,14 +476,12 @@ void csr_spmv_dot2(int nRows, const int32_t *rowPtr, const int32_t *colInd, cons
       throw std::runtime_error("csr_spmv_dot2: null pointer (the four scalars come together or not at all)");
   }
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int W = lanes - kSpmvIlp;
-  if (W != 1 && W != 2 && W != 4) throw std::runtime_error("csr_spmv_dot2: lanes must be kSpmvIlp + 1, 2 or 4");
-  const dim3 g(unsigned(spmv_dot_partial_count(nRows, W))), b(kSpmvThreads);
-  switch (W) {
-  case 1: hipLaunchKernelGGL((csr_spmv_dot2_k<1, 16>), g, b, 0, s, nRows, rowPtr, colInd, val, r, w, partialsGamma, partialsDelta, gammaOut, alphaOut, gammaPrev, alphaPrev); break;
-  case 2: hipLaunchKernelGGL((csr_spmv_dot2_k<2, 8>), g, b, 0, s, nRows, rowPtr, colInd, val, r, w, partialsGamma, partialsDelta, gammaOut, alphaOut, gammaPrev, alphaPrev); break;
-  default: hipLaunchKernelGGL((csr_spmv_dot2_k<4, 4>), g, b, 0, s, nRows, rowPtr, colInd, val, r, w, partialsGamma, partialsDelta, gammaOut, alphaOut, gammaPrev, alphaPrev); break;
-  }
+  dispatch_ilp(lanes, "csr_spmv_dot2: lanes must be kSpmvIlp + 1, 2 or 4", [&](auto lanesPerRow, auto k) {
+    constexpr int W = decltype(lanesPerRow)::value, K = decltype(k)::value;
+    const dim3 g(unsigned(spmv_dot_partial_count(nRows, W))), b(kSpmvThreads);
+    hipLaunchKernelGGL((csr_spmv_dot2_k<W, K>), g, b, 0, s, nRows, rowPtr, colInd, val, r, w, partialsGamma,
+                       partialsDelta, gammaOut, alphaOut, gammaPrev, alphaPrev);
+  });
   TZ_HIP_LAUNCH_CHECK();
 }
 

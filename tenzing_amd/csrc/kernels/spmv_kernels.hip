@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels.hpp"
+#include "launch.hpp"
 #include "spmv_device.hpp"
 
 #include <algorithm>
@@ -26,15 +27,6 @@ namespace tz {
 namespace kern {
 
 namespace {
-
-#define TZ_HIP_LAUNCH_CHECK()                                                                      \
-  do {                                                                                             \
-    hipError_t e_ = hipGetLastError();                                                             \
-    if (e_ != hipSuccess)                                                                          \
-      throw std::runtime_error(std::string("kernel launch failed: ") + hipGetErrorString(e_));     \
-  } while (0)
-
-constexpr int kThreads = 256;
 
 template <int W>
 __global__ __launch_bounds__(kThreads) void csr_spmv_k(int nRows, const int32_t *__restrict__ rowPtr,
@@ -136,22 +128,12 @@ struct DevPutBatch {
 // (IPC-mapped) remote-x buffer; the segment's last block publishes it with one system-scope
 // increment of the peer's arrival counter (same protocol as the halo puts)
 __global__ __launch_bounds__(kThreads) void gather_put_k(DevPutBatch b) {
-  int s = 0;
-  while (s + 1 < b.nseg && blockIdx.x >= b.block_start[s + 1]) ++s;
-  const PutSeg &g = b.seg[s];
-  const uint32_t nb = b.block_start[s + 1] - b.block_start[s];
-  const uint32_t tid = (blockIdx.x - b.block_start[s]) * kThreads + threadIdx.x;
-  for (uint32_t i = tid; i < uint32_t(g.n); i += nb * kThreads) g.dst[i] = b.src[b.idx[g.off + i]];
-  __threadfence_system();
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const unsigned int prev = atomicAdd(&b.done[s], 1u);
-    if (prev == nb - 1) {
-      b.done[s] = 0; // ready for the next launch (kernel boundary orders it)
-      __threadfence_system();
-      __hip_atomic_fetch_add(g.flag, 1ull, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-  }
+  const BlockSlot s = find_block(b.block_start, b.nseg, blockIdx.x);
+  const PutSeg &g = b.seg[s.entry];
+  for (uint32_t i = s.tid; i < uint32_t(g.n); i += s.nth) g.dst[i] = b.src[b.idx[g.off + i]];
+  signal_last_block(&b.done[s.entry], s.nb, [&] {
+    __hip_atomic_fetch_add(g.flag, 1ull, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+  });
 }
 
 __global__ __launch_bounds__(kThreads) void vector_add_k(int n, const float *__restrict__ a,
@@ -209,14 +191,13 @@ struct CopyBatch {
 };
 
 __global__ __launch_bounds__(kThreads) void copy_many_k(CopyBatch b) {
-  int c = 0;
-  while (c + 1 < b.n && blockIdx.x >= b.block_start[c + 1]) ++c;
-  const int64_t nb = b.block_start[c + 1] - b.block_start[c];
-  const int64_t stride = nb * kThreads;
+  const BlockSlot s = find_block(b.block_start, b.n, blockIdx.x);
+  const int c = s.entry;
+  const int64_t stride = int64_t(s.nb) * kThreads;
   int4 *__restrict__ dst = b.dst[c];
   const int4 *__restrict__ src = b.src[c];
   const int64_t n16 = b.n16[c];
-  int64_t i = int64_t(blockIdx.x - b.block_start[c]) * kThreads + threadIdx.x;
+  int64_t i = int64_t(s.blk) * kThreads + threadIdx.x;
   for (; i + 3 * stride < n16; i += 4 * stride) {
     const int4 x0 = src[i], x1 = src[i + stride], x2 = src[i + 2 * stride], x3 = src[i + 3 * stride];
     dst[i] = x0;
@@ -225,7 +206,7 @@ __global__ __launch_bounds__(kThreads) void copy_many_k(CopyBatch b) {
     dst[i + 3 * stride] = x3;
   }
   for (; i < n16; i += stride) dst[i] = src[i];
-  if (b.tail8[c] && blockIdx.x == b.block_start[c] && threadIdx.x == 0)
+  if (b.tail8[c] && s.blk == 0 && threadIdx.x == 0)
     reinterpret_cast<double *>(dst + n16)[0] = reinterpret_cast<const double *>(src + n16)[0];
 }
 
@@ -266,16 +247,12 @@ void csr_spmv(int nRows, const int32_t *rowPtr, const int32_t *colInd, const flo
     return;
   }
   if (lanesPerRow > kSpmvIlp) { // the ILP kernel with W = lanesPerRow - kSpmvIlp lanes per row
-    const int W = lanesPerRow - kSpmvIlp;
-    const int64_t threads = int64_t(nRows) * W;
-    const dim3 g(unsigned((threads + kThreads - 1) / kThreads)), b(kThreads);
-    const int acc = accumulate ? 1 : 0;
-    switch (W) {
-    case 1: hipLaunchKernelGGL((csr_spmv_ilp_k<1, 16>), g, b, 0, s, nRows, rowPtr, colInd, val, x, y, acc); break;
-    case 2: hipLaunchKernelGGL((csr_spmv_ilp_k<2, 8>), g, b, 0, s, nRows, rowPtr, colInd, val, x, y, acc); break;
-    case 4: hipLaunchKernelGGL((csr_spmv_ilp_k<4, 4>), g, b, 0, s, nRows, rowPtr, colInd, val, x, y, acc); break;
-    default: throw std::runtime_error("csr_spmv: the ILP kernel takes 1, 2 or 4 lanes per row");
-    }
+    dispatch_ilp(lanesPerRow, "csr_spmv: the ILP kernel takes 1, 2 or 4 lanes per row", [&](auto w, auto k) {
+      constexpr int W = decltype(w)::value, K = decltype(k)::value;
+      const int64_t threads = int64_t(nRows) * W;
+      const dim3 g(unsigned((threads + kThreads - 1) / kThreads)), b(kThreads);
+      hipLaunchKernelGGL((csr_spmv_ilp_k<W, K>), g, b, 0, s, nRows, rowPtr, colInd, val, x, y, accumulate ? 1 : 0);
+    });
     TZ_HIP_LAUNCH_CHECK();
     return;
   }
@@ -313,18 +290,15 @@ void gather_put_signal(const float *src, const int32_t *idx, const PutSeg *segs,
   b.src = src;
   b.idx = idx;
   b.done = done;
-  b.nseg = nseg;
-  uint32_t total = 0;
   for (int i = 0; i < nseg; ++i) {
     if (!segs[i].dst || !segs[i].flag || segs[i].n <= 0 || segs[i].off < 0)
       throw std::runtime_error("gather_put_signal: bad segment");
-    b.seg[i] = segs[i];
-    b.block_start[i] = total;
     // enough blocks to stream the segment, few enough that the completion count stays cheap
-    total += uint32_t(std::min<int64_t>(64, (int64_t(segs[i].n) + 4 * kThreads - 1) / (4 * kThreads)));
+    const int64_t blocks = std::min<int64_t>(64, (int64_t(segs[i].n) + 4 * kThreads - 1) / (4 * kThreads));
+    b.seg[append_blocks(b.block_start, b.nseg, uint32_t(blocks))] = segs[i];
   }
-  b.block_start[nseg] = total;
-  hipLaunchKernelGGL(gather_put_k, dim3(total), dim3(kThreads), 0, static_cast<hipStream_t>(stream), b);
+  hipLaunchKernelGGL(gather_put_k, dim3(b.block_start[b.nseg]), dim3(kThreads), 0,
+                     static_cast<hipStream_t>(stream), b);
   TZ_HIP_LAUNCH_CHECK();
 }
 
@@ -372,24 +346,22 @@ void copy_many(const CopyDesc *d, int n, void *stream) {
   if (n <= 0) return;
   if (n > kMaxBoxes) throw std::runtime_error("copy_many: too many copies");
   CopyBatch b{};
-  uint32_t total = 0;
   for (int i = 0; i < n; ++i) {
     if (d[i].bytes == 0) continue;
     if (!d[i].dst || !d[i].src) throw std::runtime_error("copy_many: null pointer");
     if ((reinterpret_cast<uintptr_t>(d[i].dst) | reinterpret_cast<uintptr_t>(d[i].src)) % 16 ||
         d[i].bytes % 8)
       throw std::runtime_error("copy_many: 16-byte aligned pointers and 8-byte sizes required");
-    const int k = b.n++;
+    const int64_t n16 = int64_t(d[i].bytes / 16);
+    const int k = append_blocks(b.block_start, b.n, uint32_t(grid_for(std::max<int64_t>(n16, 1), 4)));
     b.dst[k] = static_cast<int4 *>(d[i].dst);
     b.src[k] = static_cast<const int4 *>(d[i].src);
-    b.n16[k] = int64_t(d[i].bytes / 16);
+    b.n16[k] = n16;
     b.tail8[k] = int32_t((d[i].bytes % 16) / 8);
-    b.block_start[k] = total;
-    total += uint32_t(grid_for(std::max<int64_t>(b.n16[k], 1), 4));
   }
   if (b.n == 0) return;
-  b.block_start[b.n] = total;
-  hipLaunchKernelGGL(copy_many_k, dim3(total), dim3(kThreads), 0, static_cast<hipStream_t>(stream), b);
+  hipLaunchKernelGGL(copy_many_k, dim3(b.block_start[b.n]), dim3(kThreads), 0,
+                     static_cast<hipStream_t>(stream), b);
   TZ_HIP_LAUNCH_CHECK();
 }
 

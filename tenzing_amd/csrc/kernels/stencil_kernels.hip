@@ -17,6 +17,7 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels.hpp"
+#include "launch.hpp"
 
 #include <algorithm>
 #include <cstdint>
@@ -28,18 +29,9 @@ namespace kern {
 
 namespace {
 
-#define TZ_HIP_LAUNCH_CHECK()                                                                      \
-  do {                                                                                             \
-    hipError_t e_ = hipGetLastError();                                                             \
-    if (e_ != hipSuccess)                                                                          \
-      throw std::runtime_error(std::string("kernel launch failed: ") + hipGetErrorString(e_));     \
-  } while (0)
-
 constexpr int TX = 64, XS_MAX = 4;
 
 __device__ __forceinline__ double ldnt(const double *p) { return __builtin_nontemporal_load(p); }
-
-typedef double dbl2_t __attribute__((ext_vector_type(2)));
 
 // VX consecutive elements per thread (VX = 2: 16-B loads/stores of the z queue and the output)
 template <int VX> struct VT;
@@ -231,13 +223,12 @@ __device__ __forceinline__ void flat_one(const StencilBox &b, int64_t it) {
                                     in[e - b.sz] + in[e + b.sz]);
 }
 
-__global__ __launch_bounds__(256) void stencil7_flat_k(FlatBatch fb) {
-  int k = 0;
-  while (k + 1 < fb.n && blockIdx.x >= fb.block_start[k + 1]) ++k;
-  const StencilBox &b = fb.b[k];
+__global__ __launch_bounds__(kThreads) void stencil7_flat_k(FlatBatch fb) {
+  const BlockSlot s = find_block(fb.block_start, fb.n, blockIdx.x);
+  const StencilBox &b = fb.b[s.entry];
   const int64_t total = int64_t(b.row) * b.ny * b.nz * b.nouter;
-  const int64_t nth = int64_t(fb.block_start[k + 1] - fb.block_start[k]) * 256;
-  int64_t it = int64_t(blockIdx.x - fb.block_start[k]) * 256 + threadIdx.x;
+  const int64_t nth = int64_t(s.nb) * kThreads;
+  int64_t it = int64_t(s.blk) * kThreads + threadIdx.x;
   for (; it + 3 * nth < total; it += 4 * nth) {
 #pragma unroll
     for (int u = 0; u < 4; ++u) flat_one(b, it + u * nth);
@@ -253,20 +244,16 @@ void stencil7_thin_many(const StencilBox *boxes, int n, void *stream) {
   hipStream_t s = static_cast<hipStream_t>(stream);
   for (int k0 = 0; k0 < n; k0 += kMaxFlat) {
     FlatBatch fb{};
-    uint32_t total = 0;
     for (int k = k0; k < n && fb.n < kMaxFlat; ++k) {
       const StencilBox &b = boxes[k];
       const int64_t items = int64_t(b.row) * b.ny * b.nz * b.nouter;
       if (items <= 0) continue;
       if (!b.in || !b.out) throw std::runtime_error("stencil7: null grid");
-      fb.b[fb.n] = b;
-      fb.block_start[fb.n] = total;
-      total += uint32_t(std::min<int64_t>((items + 1023) / 1024, 8192)); // 4 per thread
-      ++fb.n;
+      const uint32_t blocks = uint32_t(std::min<int64_t>((items + 1023) / 1024, 8192)); // 4 per thread
+      fb.b[append_blocks(fb.block_start, fb.n, blocks)] = b;
     }
     if (fb.n == 0) continue;
-    fb.block_start[fb.n] = total;
-    hipLaunchKernelGGL(stencil7_flat_k, dim3(total), dim3(256), 0, s, fb);
+    hipLaunchKernelGGL(stencil7_flat_k, dim3(fb.block_start[fb.n]), dim3(kThreads), 0, s, fb);
     TZ_HIP_LAUNCH_CHECK();
   }
 }

@@ -62,7 +62,7 @@ std::string HaloExchange::Dir::name() const {
 
 HaloExchange::HaloExchange(HaloArgs a) : a_(std::move(a)) {
   TZ_CHECK(a_.nx > 0 && a_.ny > 0 && a_.nz > 0 && a_.nq > 0 && a_.ghost > 0, "bad halo extents");
-  // the verification values (halo_value, kernels/halo_kernels.hip) pack (gen, q, z, y, x) into
+  // the verification values (halo_value, kernels/check_kernels.hip) pack (gen, q, z, y, x) into
   // the 53 exact bits of a double: q in 3 bits below the generation, 16 bits per global axis
   TZ_CHECK(a_.nq <= 8, "at most 8 quantities per cell (got " << a_.nq
                                                              << "): the grid checks encode q in 3 bits");

@@ -1,7 +1,7 @@
 """An independent model of a completed halo exchange, in plain torch.
 
 `HaloExchange.check_grid` counts wrong cells with a device kernel whose expected values come
-from the same geometry code as the exchange itself (`csrc/kernels/halo_kernels.hip`,
+from the same geometry code as the exchange itself (`csrc/kernels/check_kernels.hip`,
 `halo_expect`). The reference has no halo output or fixture to compare against (its halo driver
 does not build at HEAD: `include/tenzing/graph.hpp:62-65` vs
 `src/halo_exchange/ops_halo_exchange.cu:50`), so this module pins the exchange to a model that

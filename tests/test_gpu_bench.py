@@ -99,7 +99,7 @@ def test_bench_plain_run_ends_with_the_headline_and_dumps_its_outputs(gpu, tmp_p
     assert ghosts.dtype == interior.dtype == np.float64
     assert interior.shape == (nq, n ** 3) and ghosts.shape == (nq, (n + 2 * g) ** 3 - n ** 3)
     assert np.array_equal(ghosts, got[1][0]) and np.array_equal(interior, got[1][1])
-    # the field of generation 0 (halo_kernels.hip, halo_value): ((q G + z) G + y) G + x, G = 2^16
+    # the field of generation 0 (check_kernels.hip, halo_value): ((q G + z) G + y) G + x, G = 2^16
     q, z, y, x = np.meshgrid(np.arange(nq), *[np.arange(n)] * 3, indexing="ij")
     field = (((q * 65536 + z) * 65536 + y) * 65536 + x).astype(np.float64)
     assert np.array_equal(interior.reshape(nq, n, n, n), field)
