@@ -1047,6 +1047,8 @@ PYBIND11_MODULE(_tz, m) {
       .def("check_stencil", [](HaloExchange &h, uintptr_t s) { return h.check_stencil(P(s)); }, py::arg("stream") = 0)
       .def("stencil", [](const HaloExchange &h, int region, uintptr_t s) { h.stencil(region, P(s)); },
            py::arg("region"), py::arg("stream") = 0)
+      .def("stencil_out_ptr", [](const HaloExchange &h) { return reinterpret_cast<uintptr_t>(h.stencil_out()); },
+           "the stencil output grid (grid_elems() doubles); 0 when not in stencil mode")
       .def("pack", [](const HaloExchange &h, int i, uintptr_t s) { h.pack(i, P(s)); })
       .def("unpack", [](const HaloExchange &h, int i, uintptr_t s) { h.unpack(i, P(s)); })
       .def("shift", [](const HaloExchange &h, int i, uintptr_t s) { h.shift(i, P(s)); })
@@ -1270,7 +1272,7 @@ PYBIND11_MODULE(_tz, m) {
            py::arg("stream") = 0, py::arg("accumulate") = false);
   k.def("stencil7", [](uintptr_t in, uintptr_t out, int64_t base, int row, int ny, int nz,
                        int nouter, int64_t sy, int64_t sz, int64_t so, int xs, double c0, double c1,
-                       bool lds, uintptr_t s) {
+                       bool lds, uintptr_t s, int m0, int m1) {
     kern::StencilBox b;
     b.in = reinterpret_cast<const double *>(in);
     b.out = reinterpret_cast<double *>(out);
@@ -1285,10 +1287,46 @@ PYBIND11_MODULE(_tz, m) {
     b.xs = xs;
     b.c0 = c0;
     b.c1 = c1;
+    b.m0 = m0;
+    b.m1 = m1;
     kern::stencil7(b, lds, P(s));
   }, py::arg("in_"), py::arg("out"), py::arg("base"), py::arg("row"), py::arg("ny"), py::arg("nz"),
      py::arg("nouter"), py::arg("sy"), py::arg("sz"), py::arg("so"), py::arg("xs"),
-     py::arg("c0") = 0.4, py::arg("c1") = 0.1, py::arg("lds") = true, py::arg("stream") = 0);
+     py::arg("c0") = 0.4, py::arg("c1") = 0.1, py::arg("lds") = true, py::arg("stream") = 0,
+     py::arg("m0") = 0, py::arg("m1") = 0);
+  k.def("stencil_thin", [](int row, int ny, int nz) {
+    kern::StencilBox b;
+    b.row = row;
+    b.ny = ny;
+    b.nz = nz;
+    return kern::stencil_thin(b);
+  }, py::arg("row"), py::arg("ny"), py::arg("nz"),
+     "whether stencil7 sends a box of these extents to the one-thread-per-element kernel");
+  k.def("stencil7_thin_many", [](uintptr_t in, uintptr_t out, std::vector<py::dict> ds, uintptr_t s) {
+    std::vector<kern::StencilBox> bs;
+    for (auto &d : ds) {
+      kern::StencilBox b;
+      b.in = reinterpret_cast<const double *>(in);
+      b.out = reinterpret_cast<double *>(out);
+      b.base = d["base"].cast<int64_t>();
+      b.sy = d["sy"].cast<int64_t>();
+      b.sz = d["sz"].cast<int64_t>();
+      b.so = d["so"].cast<int64_t>();
+      b.row = d["row"].cast<int>();
+      b.ny = d["ny"].cast<int>();
+      b.nz = d["nz"].cast<int>();
+      b.nouter = d["nouter"].cast<int>();
+      b.xs = d["xs"].cast<int>();
+      // absent: the StencilBox defaults
+      if (d.contains("m0")) b.m0 = d["m0"].cast<int>();
+      if (d.contains("m1")) b.m1 = d["m1"].cast<int>();
+      if (d.contains("c0")) b.c0 = d["c0"].cast<double>();
+      if (d.contains("c1")) b.c1 = d["c1"].cast<double>();
+      bs.push_back(b);
+    }
+    kern::stencil7_thin_many(bs.data(), int(bs.size()), P(s));
+  }, py::arg("in_"), py::arg("out"), py::arg("boxes"), py::arg("stream") = 0,
+     "the one-thread-per-element kernel over a list of boxes (dicts of the StencilBox fields)");
   k.def("set_stencil_tuning", [](int ty, int zc, int pf, bool db) {
     TZ_CHECK(ty == 8 || ty == 16, "stencil ty must be 8 or 16");
     TZ_CHECK(zc == 16 || zc == 32 || zc == 64 || zc == 128, "stencil zc must be 16, 32, 64 or 128");

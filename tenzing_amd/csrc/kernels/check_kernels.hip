@@ -87,6 +87,12 @@ __global__ __launch_bounds__(kThreads) void halo_check_k(const double *__restric
 // sees a wrong y or z neighbour at every generation. A wrong x neighbour (off by c1 * 1) is
 // below one ulp of `out` at generations 1-3 (ulp(2^51) = 0.5), so no tolerance can see it
 // there; it is seen where want is small: generation 0, q = 0.
+// Blind spot: the field is affine in (x, y, z) and c0 + 6 c1 = 1, so away from the periodic wrap
+// the stencil of the field is the field, for ANY kernel that reads a symmetric pair of
+// neighbours per axis (x twice instead of y, +-2 instead of +-1; and a ghost that the interior
+// reads beside the exchange, a race, passes whenever it already held its final value). This
+// check is the oracle for "every cell was computed after its ghosts arrived"; which neighbours
+// the kernels read is checked on random data by tests/test_gpu_stencil_kernels.py.
 __global__ __launch_bounds__(kThreads) void stencil_check_k(const double *__restrict__ out, HaloGeom g,
                                                             double c0, double c1,
                                                             unsigned long long *count) {

@@ -308,9 +308,11 @@ struct StencilBox {
   double *out = nullptr;
   int64_t base = 0, sy = 0, sz = 0, so = 0;
   int32_t row = 0, ny = 0, nz = 0, nouter = 1, xs = 1;
-  // elements at the start / end of every row that are neither stored nor read beyond: a box
-  // can keep an aligned row (16-B accesses) while excluding its first / last x cells (the
-  // ghost-free interior); the masked elements then need no apron on that side
+  // elements at the start / end of every row that are not output cells: never stored, and read
+  // only as neighbours of the output cells [m0, row - m1). A box can keep an aligned row (16-B
+  // accesses) while excluding its first / last x cells (the ghost-free interior): masked by xs
+  // or more, a side needs no x apron, and no result depends on the y / z aprons of masked
+  // elements (tenzing_amd/utils/stencil_ref.py `needed` is this rule in numpy)
   int32_t m0 = 0, m1 = 0;
   double c0 = 0.4, c1 = 0.1;
 };

@@ -242,9 +242,11 @@ bool stencil_thin(const StencilBox &b) { return b.nz < 4 || b.ny < 4 || b.row < 
 
 void stencil7_thin_many(const StencilBox *boxes, int n, void *stream) {
   hipStream_t s = static_cast<hipStream_t>(stream);
-  for (int k0 = 0; k0 < n; k0 += kMaxFlat) {
+  // a batch is the next kMaxFlat non-empty boxes: the following batch starts where this one
+  // stopped, not kMaxFlat entries on (an empty box among them would launch a box twice)
+  for (int k = 0; k < n;) {
     FlatBatch fb{};
-    for (int k = k0; k < n && fb.n < kMaxFlat; ++k) {
+    for (; k < n && fb.n < kMaxFlat; ++k) {
       const StencilBox &b = boxes[k];
       const int64_t items = int64_t(b.row) * b.ny * b.nz * b.nouter;
       if (items <= 0) continue;
