@@ -59,7 +59,8 @@ def _build_workload(a, ctrl, device, setup):
         h, s, g = build_fused(hc, sc, ctrl, device, setup, horizontal=a.horizontal == "on")
         return g, {"halo": h, "spmv": s}
     if a.workload == "cg":
-        c, g = build_cg(CgConfig(m=a.cg_m, form=a.cg_form, matrix=a.cg_matrix), ctrl, device, setup)
+        c, g = build_cg(CgConfig(m=a.cg_m, form=a.cg_form, matrix=a.cg_matrix, nrhs=a.cg_nrhs), ctrl,
+                        device, setup)
         return g, {"cg": c}
     if a.workload == "noop":
         # reference test/test_noop_graph.cpp: Start -> op1 -> Finish (here: `--noop-width`
@@ -218,7 +219,7 @@ _WORKLOAD_KEYS = ("workload", "noop_width", "streams", "halo_n", "nq", "ghost", 
                   "ipc_grid", "copy_puts", "copy_engines", "move_pairs", "horizontal",
                   "stencil", "rank_grid",
                   "spmv_m", "spmv_matrix", "spmv_form", "spmv_transport", "spmv_library",
-                  "spmv_distribute", "cg_m", "cg_form", "cg_matrix", "cg_check_iters",
+                  "spmv_distribute", "cg_m", "cg_form", "cg_matrix", "cg_nrhs", "cg_check_iters",
                   "cu_partition", "stream_priorities")
 
 
@@ -328,11 +329,14 @@ def cmd_run(a) -> int:
         ok &= out["spmv_max_rel_err"] < 1e-4
     if "cg" in wl:
         # x after cg_check_iters iterations against the same iterations in f64 on the host
+        # (the maximum over the right-hand sides)
+        cols = range(w.cg_nrhs)
         out["cg_check_iters"] = w.cg_check_iters
-        out["cg_max_rel_err"] = wl["cg"].check(w.cg_check_iters)
+        out["cg_nrhs"] = w.cg_nrhs
+        out["cg_max_rel_err"] = max(wl["cg"].check(w.cg_check_iters, j) for j in cols)
         ok &= out["cg_max_rel_err"] < 1e-4
         # the true residual ||b - A x|| / ||b|| of that x: the same quantity in every form
-        out["cg_residual"] = wl["cg"].residual()
+        out["cg_residual"] = max(wl["cg"].residual(j) for j in cols)
     rt.precompile(a.warmup)
     rt.run(a.warmup)
     rt.precompile(a.iters)  # the remainder of the unroll as one graph, compiled before timing
@@ -537,6 +541,9 @@ def _parser() -> argparse.ArgumentParser:
                         "or all three as a ChoiceOp (all)")
     s.add_argument("--cg-matrix", default="",
                    help="cg: symmetric Matrix Market file instead of the band matrix")
+    s.add_argument("--cg-nrhs", type=int, default=1,
+                   help="cg: right-hand sides solved side by side (1, 2, 4 or 8; more than one needs "
+                        "--cg-form sr): one matrix stream and one gather per entry serve all of them")
     s.add_argument("--cg-check-iters", type=int, default=25,
                    help="cg, `run`: iterations checked against the host's f64 CG (cg_max_rel_err)")
     s.set_defaults(fn=cmd_search)

@@ -1192,6 +1192,8 @@ PYBIND11_MODULE(_tz, m) {
       .def_readwrite("form", &CgArgs::form)
       .def_readwrite("lanes", &CgArgs::lanes)
       .def_readwrite("rhs", &CgArgs::rhs)
+      .def_readwrite("nrhs", &CgArgs::nrhs)
+      .def_readwrite("rhs_first", &CgArgs::rhs_first)
       .def_readwrite("prefix", &CgArgs::prefix)
       .def_readwrite("rank", &CgArgs::rank)
       .def_readwrite("size", &CgArgs::size)
@@ -1211,14 +1213,18 @@ PYBIND11_MODULE(_tz, m) {
         .def("add_to_graph", &ConjugateGradient::add_to_graph)
         .def("reset", &ConjugateGradient::reset, py::call_guard<py::gil_scoped_release>(),
              "x = 0, r = p = b, rr = b . b (synchronous)")
-        .def("x", [f32](const ConjugateGradient &c) { return f32(c.x()); })
-        .def("r", [f32](const ConjugateGradient &c) { return f32(c.r()); })
-        .def("p", [f32](const ConjugateGradient &c) { return f32(c.p()); })
-        .def("b", [f32](const ConjugateGradient &c) { return f32(c.b()); })
-        .def("rr", &ConjugateGradient::rr, "r . r of the current residual (f64, the kernels' summation order)")
-        .def("check", &ConjugateGradient::check, py::arg("k"), py::call_guard<py::gil_scoped_release>(),
+        .def("x", [f32](const ConjugateGradient &c, int col) { return f32(c.x(col)); }, py::arg("col") = 0,
+             "column col (0 .. nrhs - 1) of x, de-interleaved; likewise r, p, b, rr, check and residual")
+        .def("r", [f32](const ConjugateGradient &c, int col) { return f32(c.r(col)); }, py::arg("col") = 0)
+        .def("p", [f32](const ConjugateGradient &c, int col) { return f32(c.p(col)); }, py::arg("col") = 0)
+        .def("b", [f32](const ConjugateGradient &c, int col) { return f32(c.b(col)); }, py::arg("col") = 0)
+        .def("rr", &ConjugateGradient::rr, py::arg("col") = 0,
+             "r . r of the current residual (f64, the kernels' summation order)")
+        .def("check", &ConjugateGradient::check, py::arg("k"), py::arg("col") = 0,
+             py::call_guard<py::gil_scoped_release>(),
              "max |x - x_ref| / max |x_ref| against k host iterations in f64")
-        .def("residual", &ConjugateGradient::residual, py::call_guard<py::gil_scoped_release>(),
+        .def("residual", &ConjugateGradient::residual, py::arg("col") = 0,
+             py::call_guard<py::gil_scoped_release>(),
              "the true residual ||b - A x|| / ||b|| of the current x, in f64 on the host");
   }
   m.def("read_matrix_market", [](const std::string &path) {
@@ -1418,6 +1424,31 @@ PYBIND11_MODULE(_tz, m) {
   }, py::arg("n"), py::arg("partials_gamma"), py::arg("partials_delta"), py::arg("np"), py::arg("gamma_prev"),
      py::arg("alpha_prev"), py::arg("w"), py::arg("r"), py::arg("p"), py::arg("s"), py::arg("x"),
      py::arg("gamma_out"), py::arg("alpha_out"), py::arg("beta_out"), py::arg("stream") = 0);
+  k.def("csr_spmm_dot2", [](int n, uintptr_t rp, uintptr_t ci, uintptr_t v, uintptr_t r, uintptr_t w, int nrhs,
+                            int lanes, uintptr_t pg, uintptr_t pd, uintptr_t gOut, uintptr_t aOut,
+                            uintptr_t gPrev, uintptr_t aPrev, uintptr_t s) {
+    kern::csr_spmm_dot2(n, reinterpret_cast<const int32_t *>(rp), reinterpret_cast<const int32_t *>(ci),
+                        reinterpret_cast<const float *>(v), reinterpret_cast<const float *>(r),
+                        reinterpret_cast<float *>(w), nrhs, lanes, reinterpret_cast<double *>(pg),
+                        reinterpret_cast<double *>(pd), reinterpret_cast<const double *>(gOut),
+                        reinterpret_cast<const double *>(aOut), reinterpret_cast<double *>(gPrev),
+                        reinterpret_cast<double *>(aPrev), P(s));
+  }, py::arg("n_rows"), py::arg("row_ptr"), py::arg("col_ind"), py::arg("val"), py::arg("r"), py::arg("w"),
+     py::arg("k"), py::arg("lanes"), py::arg("partials_gamma"), py::arg("partials_delta"),
+     py::arg("gamma_out") = 0, py::arg("alpha_out") = 0, py::arg("gamma_prev") = 0, py::arg("alpha_prev") = 0,
+     py::arg("stream") = 0);
+  k.def("cg_sr_update_batch", [](int64_t n, int nrhs, uintptr_t pg, uintptr_t pd, int np, uintptr_t gPrev,
+                                 uintptr_t aPrev, uintptr_t w, uintptr_t r, uintptr_t p, uintptr_t sv, uintptr_t x,
+                                 uintptr_t gOut, uintptr_t aOut, uintptr_t bOut, uintptr_t s) {
+    kern::cg_sr_update_batch(n, nrhs, reinterpret_cast<const double *>(pg), reinterpret_cast<const double *>(pd),
+                             np, reinterpret_cast<const double *>(gPrev), reinterpret_cast<const double *>(aPrev),
+                             reinterpret_cast<const float *>(w), reinterpret_cast<float *>(r),
+                             reinterpret_cast<float *>(p), reinterpret_cast<float *>(sv),
+                             reinterpret_cast<float *>(x), reinterpret_cast<double *>(gOut),
+                             reinterpret_cast<double *>(aOut), reinterpret_cast<double *>(bOut), P(s));
+  }, py::arg("n"), py::arg("k"), py::arg("partials_gamma"), py::arg("partials_delta"), py::arg("np"),
+     py::arg("gamma_prev"), py::arg("alpha_prev"), py::arg("w"), py::arg("r"), py::arg("p"), py::arg("s"),
+     py::arg("x"), py::arg("gamma_out"), py::arg("alpha_out"), py::arg("beta_out"), py::arg("stream") = 0);
   k.def("gather_f32", [](int n, uintptr_t src, uintptr_t idx, uintptr_t dst, uintptr_t s) {
     kern::gather_f32(n, reinterpret_cast<const float *>(src), reinterpret_cast<const int32_t *>(idx),
                      reinterpret_cast<float *>(dst), P(s));

@@ -1,6 +1,7 @@
 // Conjugate-gradient kernels for gfx950: dot products, vector updates whose coefficient lives in
 // device memory, the fused forms (SpMV + dot, update + dot) and the single-reduction form's two
-// kernels (SpMV + two dots, one update of p, s, x and r). Not in the reference.
+// kernels (SpMV + two dots, one update of p, s, x and r), those two also for 2, 4 or 8 interleaved
+// right-hand sides. Not in the reference.
 //
 // Vectors are f32; dot products accumulate in f64 (the product of two f32 values is exact in
 // f64); every scalar (rr, alpha, beta) is an f64 in device memory, so no launch argument carries
@@ -283,6 +284,76 @@ __global__ __launch_bounds__(kSpmvThreads) void csr_spmv_dot2_k(int nRows, const
   }
 }
 
+// N block_sums behind one barrier, for a block whose result only leaves through one store per
+// value: the same butterfly per value, then thread i < N adds the NW wave sums of value i in wave
+// order and returns block_sum<NW>(v[i])'s bits (other threads: unspecified). sh: N * NW doubles.
+template <int NW, int N> __device__ __forceinline__ double block_sum_n(double (&v)[N], double *sh) {
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v[i] += __shfl_xor(v[i], off, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) sh[i * NW + (threadIdx.x >> 6)] = v[i];
+  }
+  __syncthreads();
+  const int i = int(threadIdx.x) < N ? int(threadIdx.x) : 0;
+  double s = sh[i * NW];
+#pragma unroll
+  for (int w = 1; w < NW; ++w) s += sh[i * NW + w];
+  return s;
+}
+
+// csr_spmv_dot2_k for NR right-hand sides, interleaved (element (i, j) of R and Wout at i * NR +
+// j): the same grid and the same row -> lane group -> block mapping, and per column the same
+// entry order, fmaf chain, xor reduction and block_sum (dev::csr_spmm_ilp_sum, block_sum_n). So
+// column j of Wout and slab j of both partial arrays (slab j starts at j * kCgMaxPartials) have
+// the bits csr_spmv_dot2_k writes for column j alone, while the matrix is streamed once and an
+// entry's NR x values come from one line. Block 0 moves the NR published gammas and alphas.
+template <int W, int K, int NR>
+__global__ __launch_bounds__(kSpmvThreads) void csr_spmm_dot2_k(int nRows, const int32_t *__restrict__ rowPtr,
+                                                                const int32_t *__restrict__ colInd,
+                                                                const float *__restrict__ val,
+                                                                const float *__restrict__ r,
+                                                                float *__restrict__ w,
+                                                                double *__restrict__ partialsGamma,
+                                                                double *__restrict__ partialsDelta,
+                                                                const double *__restrict__ gammaOut,
+                                                                const double *__restrict__ alphaOut,
+                                                                double *__restrict__ gammaPrev,
+                                                                double *__restrict__ alphaPrev) {
+  __shared__ double sh[2 * NR * (kSpmvThreads / 64)];
+  if (gammaOut && blockIdx.x == 0 && int(threadIdx.x) < NR) {
+    gammaPrev[threadIdx.x] = gammaOut[threadIdx.x];
+    alphaPrev[threadIdx.x] = alphaOut[threadIdx.x];
+  }
+  const int lane = threadIdx.x & (W - 1);
+  const int rowsPerPass = int(gridDim.x) * (kSpmvThreads / W);
+  double acc[2 * NR]; // gamma of column j at j, delta at NR + j
+#pragma unroll
+  for (int j = 0; j < 2 * NR; ++j) acc[j] = 0.0;
+  // whole W-lane groups leave the loop together (W divides 64)
+  for (int row = (blockIdx.x * kSpmvThreads + threadIdx.x) / W; row < nRows; row += rowsPerPass) {
+    float sum[NR];
+    dev::csr_spmm_ilp_sum<W, K, NR>(row, lane, rowPtr, colInd, val, r, sum);
+    if (lane == 0) {
+      float ri[NR];
+      dev::load_row<NR>(r + int64_t(row) * NR, ri);
+      dev::store_row<NR>(w + int64_t(row) * NR, sum);
+#pragma unroll
+      for (int j = 0; j < NR; ++j) {
+        acc[j] += double(ri[j]) * double(ri[j]);
+        acc[NR + j] += double(ri[j]) * double(sum[j]);
+      }
+    }
+  }
+  const double sum = block_sum_n<kSpmvThreads / 64, 2 * NR>(acc, sh);
+  const int t = threadIdx.x; // thread j writes gamma's slab j, thread NR + j delta's
+  if (t < NR) partialsGamma[t * kCgMaxPartials + blockIdx.x] = sum;
+  else if (t < 2 * NR) partialsDelta[(t - NR) * kCgMaxPartials + blockIdx.x] = sum;
+}
+
 // alpha = gamma / (delta - beta * (gamma / alphaPrev)), every division guarded. The product and
 // the difference round separately (no fma), so the bits are those of the same expression in any
 // IEEE f64 arithmetic. This file is built with -ffp-contract=fast, which disregards `#pragma
@@ -340,6 +411,91 @@ __global__ __launch_bounds__(kThreads) void cg_sr_update_k(int64_t n, const doub
     s[t] = st;
     x[t] = fmaf(a, pt, x[t]);
     r[t] = fmaf(na, st, rt);
+  }
+}
+
+// cg_sr_update_k for NR right-hand sides, interleaved: one pass over the n * NR elements in the
+// quad layout, every column with its own beta and alpha. A thread's quads always hold the same
+// columns (the pass stride, blocks * 256 quads, is a multiple of NR elements), so it keeps four
+// (beta, alpha) pairs in registers. The prologue sums the 2 NR slabs together: thread t holds
+// partial t of each, one butterfly per slab, one barrier, then thread j < NR adds the four wave
+// sums of gamma_j and delta_j in wave order (the bits of sum_partials), forms beta_j and alpha_j
+// as cg_sr_update_k does and leaves them, rounded to f32, in LDS for the block.
+template <int NR>
+__global__ __launch_bounds__(kThreads) void cg_sr_update_batch_k(
+    int64_t n, const double *__restrict__ partialsGamma, const double *__restrict__ partialsDelta, int np,
+    const double *__restrict__ gammaPrev, const double *__restrict__ alphaPrev, const float *w, float *r,
+    float *p, float *s, float *x, double *__restrict__ gammaOut, double *__restrict__ alphaOut,
+    double *__restrict__ betaOut) {
+  constexpr int NW = kThreads / 64;
+  __shared__ double sh[2 * NR * NW];
+  __shared__ float shB[NR], shA[NR];
+  const int tid = threadIdx.x;
+  double v[2 * NR]; // gamma of column j at j, delta at NR + j
+#pragma unroll
+  for (int j = 0; j < NR; ++j) {
+    v[j] = tid < np ? partialsGamma[j * kCgMaxPartials + tid] : 0.0;
+    v[NR + j] = tid < np ? partialsDelta[j * kCgMaxPartials + tid] : 0.0;
+  }
+#pragma unroll
+  for (int i = 0; i < 2 * NR; ++i) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v[i] += __shfl_xor(v[i], off, 64);
+  }
+  if ((tid & 63) == 0) {
+#pragma unroll
+    for (int i = 0; i < 2 * NR; ++i) sh[i * NW + (tid >> 6)] = v[i];
+  }
+  __syncthreads();
+  if (tid < NR) {
+    double gamma = sh[tid * NW], delta = sh[(NR + tid) * NW];
+#pragma unroll
+    for (int wv = 1; wv < NW; ++wv) {
+      gamma += sh[tid * NW + wv];
+      delta += sh[(NR + tid) * NW + wv];
+    }
+    const double beta = guarded_div(gamma, gammaPrev[tid]);
+    const double alpha = sr_alpha(gamma, delta, beta, alphaPrev[tid]);
+    if (blockIdx.x == 0) {
+      gammaOut[tid] = gamma;
+      alphaOut[tid] = alpha;
+      betaOut[tid] = beta;
+    }
+    shB[tid] = float(beta);
+    shA[tid] = float(alpha);
+  }
+  __syncthreads();
+  const int col0 = (4 * tid) & (NR - 1);
+  float b[4], a[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    b[i] = shB[(col0 + i) & (NR - 1)];
+    a[i] = shA[(col0 + i) & (NR - 1)];
+  }
+  const int64_t total = n * NR, nq = total / 4, stride = int64_t(gridDim.x) * kThreads;
+  for (int64_t k = int64_t(blockIdx.x) * kThreads + tid; k < nq; k += stride) {
+    const float4 wv = load_quad(w, k, true);
+    float4 rv = load_quad(r, k, true), pv = load_quad(p, k, true), sv = load_quad(s, k, true),
+           xv = load_quad(x, k, true);
+    pv.x = fmaf(b[0], pv.x, rv.x), pv.y = fmaf(b[1], pv.y, rv.y), pv.z = fmaf(b[2], pv.z, rv.z), pv.w = fmaf(b[3], pv.w, rv.w);
+    sv.x = fmaf(b[0], sv.x, wv.x), sv.y = fmaf(b[1], sv.y, wv.y), sv.z = fmaf(b[2], sv.z, wv.z), sv.w = fmaf(b[3], sv.w, wv.w);
+    xv.x = fmaf(a[0], pv.x, xv.x), xv.y = fmaf(a[1], pv.y, xv.y), xv.z = fmaf(a[2], pv.z, xv.z), xv.w = fmaf(a[3], pv.w, xv.w);
+    rv.x = fmaf(-a[0], sv.x, rv.x), rv.y = fmaf(-a[1], sv.y, rv.y), rv.z = fmaf(-a[2], sv.z, rv.z), rv.w = fmaf(-a[3], sv.w, rv.w);
+    store_quad(p, k, true, pv);
+    store_quad(s, k, true, sv);
+    store_quad(x, k, true, xv);
+    store_quad(r, k, true, rv);
+  }
+  // the total % 4 tail elements (NR = 2 with an odd n only)
+  const int64_t t = nq * 4 + tid;
+  if (blockIdx.x == 0 && t < total) {
+    const float bt = shB[t & (NR - 1)], at = shA[t & (NR - 1)];
+    const float rt = r[t];
+    const float pt = fmaf(bt, p[t], rt), st = fmaf(bt, s[t], w[t]);
+    p[t] = pt;
+    s[t] = st;
+    x[t] = fmaf(at, pt, x[t]);
+    r[t] = fmaf(-at, st, rt);
   }
 }
 
@@ -502,6 +658,88 @@ void cg_sr_update(int64_t n, const double *partialsGamma, const double *partials
   hipLaunchKernelGGL(cg_sr_update_k, dim3(dot_partial_count(n)), dim3(kThreads), 0,
                      static_cast<hipStream_t>(stream), n, partialsGamma, partialsDelta, np, gammaPrev, alphaPrev,
                      w, r, p, s, x, gammaOut, alphaOut, betaOut);
+  TZ_HIP_LAUNCH_CHECK();
+}
+
+namespace {
+
+// f(Int<NR>) for k = NR right-hand sides
+template <typename F> void dispatch_nrhs(int k, const char *what, F &&f) {
+  switch (k) {
+  case 2: f(Int<2>{}); break;
+  case 4: f(Int<4>{}); break;
+  case 8: f(Int<8>{}); break;
+  default: throw std::runtime_error(std::string(what) + ": k must be 2, 4 or 8 right-hand sides");
+  }
+}
+
+void check_batch_vec(const char *what, const void *a) {
+  if (!a) throw std::runtime_error(std::string(what) + ": null pointer");
+  if (reinterpret_cast<uintptr_t>(a) % 16)
+    throw std::runtime_error(std::string(what) + ": batched vectors must be 16-byte aligned");
+}
+
+// k doubles at a and k doubles at b share a byte
+bool overlap(const double *a, const double *b, int k) { return a < b + k && b < a + k; }
+
+} // namespace
+
+void csr_spmm_dot2(int nRows, const int32_t *rowPtr, const int32_t *colInd, const float *val, const float *R,
+                   float *Wout, int k, int lanes, double *partialsGamma, double *partialsDelta,
+                   const double *gammaOut, const double *alphaOut, double *gammaPrev, double *alphaPrev,
+                   void *stream) {
+  if (nRows <= 0) throw std::runtime_error("csr_spmm_dot2: nRows must be positive");
+  if (k != 2 && k != 4 && k != 8) throw std::runtime_error("csr_spmm_dot2: k must be 2, 4 or 8 right-hand sides");
+  if (!rowPtr || !colInd || !val || !partialsGamma || !partialsDelta)
+    throw std::runtime_error("csr_spmm_dot2: null pointer");
+  check_batch_vec("csr_spmm_dot2", R);
+  check_batch_vec("csr_spmm_dot2", Wout);
+  if (R == Wout) throw std::runtime_error("csr_spmm_dot2: R and Wout must differ");
+  if (overlap(partialsGamma, partialsDelta, k * kCgMaxPartials))
+    throw std::runtime_error("csr_spmm_dot2: the two slab arrays must not overlap");
+  if (gammaOut || alphaOut || gammaPrev || alphaPrev) {
+    if (!gammaOut || !alphaOut || !gammaPrev || !alphaPrev)
+      throw std::runtime_error("csr_spmm_dot2: null pointer (the four scalar arrays come together or not at all)");
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  dispatch_ilp(lanes, "csr_spmm_dot2: lanes must be kSpmvIlp + 1, 2 or 4", [&](auto lanesPerRow, auto depth) {
+    constexpr int W = decltype(lanesPerRow)::value, K = decltype(depth)::value;
+    dispatch_nrhs(k, "csr_spmm_dot2", [&](auto nr) {
+      constexpr int NR = decltype(nr)::value;
+      const dim3 g(unsigned(spmv_dot_partial_count(nRows, W))), b(kSpmvThreads);
+      hipLaunchKernelGGL((csr_spmm_dot2_k<W, K, NR>), g, b, 0, s, nRows, rowPtr, colInd, val, R, Wout,
+                         partialsGamma, partialsDelta, gammaOut, alphaOut, gammaPrev, alphaPrev);
+    });
+  });
+  TZ_HIP_LAUNCH_CHECK();
+}
+
+void cg_sr_update_batch(int64_t n, int k, const double *partialsGamma, const double *partialsDelta, int np,
+                        const double *gammaPrev, const double *alphaPrev, const float *W, float *R, float *P,
+                        float *S, float *X, double *gammaOut, double *alphaOut, double *betaOut, void *stream) {
+  if (n <= 0) throw std::runtime_error("cg_sr_update_batch: n must be positive");
+  if (k != 2 && k != 4 && k != 8)
+    throw std::runtime_error("cg_sr_update_batch: k must be 2, 4 or 8 right-hand sides");
+  for (const void *v : {static_cast<const void *>(W), static_cast<const void *>(R), static_cast<const void *>(P),
+                        static_cast<const void *>(S), static_cast<const void *>(X)})
+    check_batch_vec("cg_sr_update_batch", v);
+  check_np("cg_sr_update_batch", partialsGamma, np);
+  check_np("cg_sr_update_batch", partialsDelta, np);
+  if (!gammaPrev || !alphaPrev || !gammaOut || !alphaOut || !betaOut)
+    throw std::runtime_error("cg_sr_update_batch: null pointer");
+  // a block reads gammaPrev / alphaPrev while block 0 may already have published
+  for (const double *out : {gammaOut, alphaOut, betaOut})
+    if (overlap(out, gammaPrev, k) || overlap(out, alphaPrev, k))
+      throw std::runtime_error("cg_sr_update_batch: the published scalars must not alias the previous ones");
+  if (overlap(gammaOut, alphaOut, k) || overlap(gammaOut, betaOut, k) || overlap(alphaOut, betaOut, k))
+    throw std::runtime_error("cg_sr_update_batch: the three published arrays must not alias each other");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  dispatch_nrhs(k, "cg_sr_update_batch", [&](auto nr) {
+    constexpr int NR = decltype(nr)::value;
+    hipLaunchKernelGGL((cg_sr_update_batch_k<NR>), dim3(dot_partial_count(n * k)), dim3(kThreads), 0, s, n,
+                       partialsGamma, partialsDelta, np, gammaPrev, alphaPrev, W, R, P, S, X, gammaOut, alphaOut,
+                       betaOut);
+  });
   TZ_HIP_LAUNCH_CHECK();
 }
 

@@ -280,6 +280,25 @@ void csr_spmv_dot2(int nRows, const int32_t *rowPtr, const int32_t *colInd, cons
 void cg_sr_update(int64_t n, const double *partials_gamma, const double *partials_delta, int np,
                   const double *gamma_prev, const double *alpha_prev, const float *w, float *r, float *p, float *s,
                   float *x, double *gamma_out, double *alpha_out, double *beta_out, void *stream);
+// ---- the same two launches for k = 2, 4 or 8 right-hand sides. A batched vector is n x k f32,
+// row-major (element (i, j) at i * k + j: row i of all k vectors is 4 k <= 32 bytes inside one
+// 128-byte line) and 16-byte aligned; batched slabs are k consecutive slabs of kCgMaxPartials
+// doubles (column j's at + j * kCgMaxPartials); a batched scalar is an array of k doubles. Every
+// column is computed exactly as the single kernels compute it alone: same bits.
+/// Wout[:, j] = A R[:, j] and block b's shares of R[:, j] . R[:, j] and R[:, j] . Wout[:, j] in
+/// slab j of partials_gamma / partials_delta; grid, row mapping, per-lane entry order and sums as
+/// csr_spmv_dot2 (`lanes` likewise), so column j has the bits of csr_spmv_dot2 on column j alone.
+/// With the four scalar arrays (all or none) block 0 copies k gammas and k alphas.
+void csr_spmm_dot2(int nRows, const int32_t *rowPtr, const int32_t *colInd, const float *val, const float *R,
+                   float *Wout, int k, int lanes, double *partials_gamma, double *partials_delta,
+                   const double *gamma_out, const double *alpha_out, double *gamma_prev, double *alpha_prev,
+                   void *stream);
+/// cg_sr_update for every column j with its own gamma_j, delta_j (slab j, np partials each),
+/// gamma_prev[j], alpha_prev[j]: one pass over the n k elements. Block 0 stores k gammas, alphas
+/// and betas to arrays that must not overlap gamma_prev / alpha_prev.
+void cg_sr_update_batch(int64_t n, int k, const double *partials_gamma, const double *partials_delta, int np,
+                        const double *gamma_prev, const double *alpha_prev, const float *W, float *R, float *P,
+                        float *S, float *X, double *gamma_out, double *alpha_out, double *beta_out, void *stream);
 
 /// y += alpha * x (f64)
 void axpy_f64(int64_t n, double alpha, const double *x, double *y, void *stream);

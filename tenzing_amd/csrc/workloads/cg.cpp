@@ -16,7 +16,9 @@
 //          slab's place) and delta slab (the pq slab's) <- spmvdot; gamma, alpha, beta <- block 0
 //          of the update, which no block of that launch reads; gamma_prev, alpha_prev <- block 0
 //          of the next iteration's spmvdot, which copies them from gamma and alpha (after their
-//          last reader, the update, and before the next one)
+//          last reader, the update, and before the next one). With nrhs = 2, 4 or 8 the same
+//          two ops run the batched kernels on interleaved vectors: nrhs independent recurrences,
+//          every slab and scalar an array of nrhs with the same writers
 #include "workloads.hpp"
 
 #include "core/util.hpp"
@@ -41,6 +43,8 @@ Json CgArgs::json() const {
   j["form"] = form;
   j["lanes"] = lanes;
   j["rhs"] = rhs;
+  j["nrhs"] = nrhs;
+  j["rhs_first"] = rhs_first;
   j["rank"] = rank;
   j["size"] = size;
   return j;
@@ -100,6 +104,13 @@ ConjugateGradient::ConjugateGradient(CgArgs a) : a_(std::move(a)) {
   TZ_CHECK(a_.form == "choice" || a_.form == "plain" || a_.form == "fused" || a_.form == "sr" || a_.form == "all",
            "CG form must be choice, plain, fused, sr or all (got " << a_.form << ")");
   TZ_CHECK(a_.rhs == "random" || a_.rhs == "zero", "CG rhs must be random or zero (got " << a_.rhs << ")");
+  TZ_CHECK(a_.nrhs == 1 || a_.nrhs == 2 || a_.nrhs == 4 || a_.nrhs == 8,
+           "CG nrhs must be 1, 2, 4 or 8 right-hand sides (got " << a_.nrhs << "): a row of the batch is one "
+               << "16-byte-aligned run inside a 128-byte line");
+  TZ_CHECK(a_.nrhs == 1 || a_.form == "sr",
+           "CG with nrhs > 1 needs form sr: only the single-reduction form has batched kernels (got nrhs "
+               << a_.nrhs << " with form " << a_.form << ")");
+  TZ_CHECK(a_.rhs_first >= 0, "CG rhs_first must not be negative (got " << a_.rhs_first << ")");
   if (!a_.matrix.empty()) {
     A_ = read_matrix_market(a_.matrix);
     TZ_CHECK(A_.rows == A_.cols, a_.matrix << ": CG needs a square matrix, got " << A_.rows << " x " << A_.cols);
@@ -124,11 +135,15 @@ ConjugateGradient::ConjugateGradient(CgArgs a) : a_(std::move(a)) {
   }
   TZ_CHECK(A_.rows < (int64_t(1) << 31) / 4, "CG: too many rows");
   a_.nnz_actual = A_.nnz();
-  b_.assign(size_t(A_.rows), 0.f);
+  b_.assign(size_t(a_.nrhs), std::vector<float>(size_t(A_.rows), 0.f));
   if (a_.rhs == "random") {
-    // 24 random bits per entry: k / 2^23 - 1 is exact in f32 and lies in [-1, 1)
-    std::mt19937_64 rng(a_.seed ^ 0xC6A4A7935BD1E995ull);
-    for (float &v : b_) v = float(int64_t(rng() >> 40)) / 8388608.f - 1.f;
+    for (int c = 0; c < a_.nrhs; ++c) {
+      // 24 random bits per entry: k / 2^23 - 1 is exact in f32 and lies in [-1, 1). Right-hand
+      // side number j of the sequence reseeds the generator (j = 0: the single solve's b).
+      const uint64_t j = uint64_t(a_.rhs_first) + uint64_t(c);
+      std::mt19937_64 rng((a_.seed ^ 0xC6A4A7935BD1E995ull) + j * 0x9E3779B97F4A7C15ull);
+      for (float &v : b_[size_t(c)]) v = float(int64_t(rng() >> 40)) / 8388608.f - 1.f;
+    }
   }
   const int W = a_.lanes - kern::kSpmvIlp;
   TZ_CHECK(a_.lanes == -1 || a_.lanes == 0 || W == 1 || W == 2 || W == 4 ||
@@ -146,14 +161,20 @@ void ConjugateGradient::setup() {
   up(dRow_, A_.rowPtr.data(), A_.rowPtr.size() * 4);
   up(dCol_, A_.colInd.data(), A_.colInd.size() * 4);
   up(dVal_, A_.val.data(), A_.val.size() * 4);
-  up(dB_, b_.data(), b_.size() * 4);
-  const size_t vb = std::max<size_t>(size_t(rows()) * 4, 16);
+  // the right-hand sides as the kernels hold every vector: element (i, j) at i * nrhs + j
+  const size_t k = size_t(a_.nrhs);
+  std::vector<float> bi(size_t(rows()) * k);
+  for (size_t c = 0; c < k; ++c)
+    for (size_t i = 0; i < size_t(rows()); ++i) bi[i * k + c] = b_[c][i];
+  up(dB_, bi.data(), bi.size() * 4);
+  const size_t vb = std::max<size_t>(size_t(rows()) * k * 4, 16);
   dR_ = DeviceBuffer(vb);
   dP_ = DeviceBuffer(vb);
   dQ_ = DeviceBuffer(vb);
   dS_ = DeviceBuffer(vb);
   dW_ = DeviceBuffer(vb);
   dScal_ = DeviceBuffer((3 * size_t(kern::kCgMaxPartials) + 8) * sizeof(double));
+  if (a_.nrhs > 1) dBatch_ = DeviceBuffer((2 * size_t(kern::kCgMaxPartials) + 5) * k * sizeof(double));
   dX_ = DeviceBuffer(vb);
   reset();
 }
@@ -162,7 +183,7 @@ void ConjugateGradient::reset() {
   TZ_CHECK(ready(), "CG not set up");
   // synchronous: schedules run on non-blocking streams that do not order after the null stream
   TZ_HIP(hipDeviceSynchronize());
-  const size_t vb = size_t(rows()) * 4;
+  const size_t vb = size_t(rows()) * size_t(a_.nrhs) * 4;
   TZ_HIP(hipMemset(dX_.get(), 0, dX_.bytes()));
   TZ_HIP(hipMemset(dQ_.get(), 0, dQ_.bytes()));
   TZ_HIP(hipMemset(dS_.get(), 0, dS_.bytes()));
@@ -170,48 +191,73 @@ void ConjugateGradient::reset() {
   TZ_HIP(hipMemset(dScal_.get(), 0, dScal_.bytes()));
   TZ_HIP(hipMemcpy(dR_.get(), dB_.get(), vb, hipMemcpyDeviceToDevice));
   TZ_HIP(hipMemcpy(dP_.get(), dB_.get(), vb, hipMemcpyDeviceToDevice));
+  if (a_.nrhs > 1) { // the batched form keeps no rr: every scalar array starts at 0
+    TZ_HIP(hipMemset(dBatch_.get(), 0, dBatch_.bytes()));
+    TZ_HIP(hipDeviceSynchronize());
+    return;
+  }
   kern::dot_partials_f32(rows(), dR_.as<float>(), dR_.as<float>(), rrp_(), nullptr);
   kern::sum_partials_f64(rrp_(), np_vec(), rr_(), nullptr);
   TZ_HIP(hipDeviceSynchronize());
 }
 
-std::vector<float> ConjugateGradient::down(const DeviceBuffer &d) const {
+int ConjugateGradient::checked(int col) const {
+  TZ_CHECK(col >= 0 && col < a_.nrhs, "CG column " << col << " out of range: " << a_.nrhs << " right-hand side(s)");
+  return col;
+}
+
+std::vector<float> ConjugateGradient::down(const DeviceBuffer &d, int col) const {
   TZ_CHECK(ready(), "CG not set up");
+  const size_t k = size_t(a_.nrhs), c = size_t(checked(col));
   TZ_HIP(hipDeviceSynchronize());
+  std::vector<float> all(static_cast<size_t>(rows()) * k);
+  d.download(all.data(), all.size() * 4);
+  if (k == 1) return all;
   std::vector<float> v(static_cast<size_t>(rows()));
-  d.download(v.data(), v.size() * 4);
+  for (size_t i = 0; i < v.size(); ++i) v[i] = all[i * k + c];
   return v;
 }
 
-double ConjugateGradient::rr() const {
+double ConjugateGradient::rr(int col) const {
   TZ_CHECK(ready(), "CG not set up");
+  checked(col);
   TZ_HIP(hipDeviceSynchronize());
   // from r itself: the single-reduction form's slabs hold the previous r's products. The layout
   // is dot_rr's and the fused r update's, so for those forms these are the bits of the rr slab.
-  kern::dot_partials_f32(rows(), dR_.as<float>(), dR_.as<float>(), scratch_(), nullptr);
-  TZ_HIP(hipDeviceSynchronize());
+  if (a_.nrhs > 1) { // a contiguous copy of the column: the layout, hence the bits, of a single solve
+    const std::vector<float> rc = r(col);
+    DeviceBuffer tmp(std::max<size_t>(rc.size() * 4, 16));
+    tmp.upload(rc.data(), rc.size() * 4);
+    kern::dot_partials_f32(rows(), tmp.as<float>(), tmp.as<float>(), scratch_(), nullptr);
+    TZ_HIP(hipDeviceSynchronize());
+  } else {
+    kern::dot_partials_f32(rows(), dR_.as<float>(), dR_.as<float>(), scratch_(), nullptr);
+    TZ_HIP(hipDeviceSynchronize());
+  }
   std::vector<double> part(static_cast<size_t>(kern::kCgMaxPartials), 0.0);
   TZ_HIP(hipMemcpy(part.data(), scratch_(), size_t(np_vec()) * sizeof(double), hipMemcpyDeviceToHost));
   return sum_partials_host(part.data(), np_vec());
 }
 
-double ConjugateGradient::residual() const {
-  const std::vector<float> xd = this->x();
+double ConjugateGradient::residual(int col) const {
+  const std::vector<float> xd = this->x(col);
+  const std::vector<float> &bc = this->b(col);
   double res = 0, bb = 0;
   for (size_t i = 0; i < size_t(rows()); ++i) {
     double s = 0;
     for (int32_t j = A_.rowPtr[i]; j < A_.rowPtr[i + 1]; ++j)
       s += double(A_.val[size_t(j)]) * double(xd[size_t(A_.colInd[size_t(j)])]);
-    const double d = double(b_[i]) - s;
+    const double d = double(bc[i]) - s;
     res += d * d;
-    bb += double(b_[i]) * double(b_[i]);
+    bb += double(bc[i]) * double(bc[i]);
   }
   return bb > 0 ? std::sqrt(res / bb) : std::sqrt(res);
 }
 
-double ConjugateGradient::check(int k) const {
+double ConjugateGradient::check(int k, int col) const {
   const size_t n = size_t(rows());
-  std::vector<double> x(n, 0.0), r(b_.begin(), b_.end()), p(r), q(n);
+  const std::vector<float> &bc = this->b(col);
+  std::vector<double> x(n, 0.0), r(bc.begin(), bc.end()), p(r), q(n);
   double rr = 0;
   for (size_t i = 0; i < n; ++i) rr += r[i] * r[i];
   for (int it = 0; it < k; ++it) {
@@ -234,7 +280,7 @@ double ConjugateGradient::check(int k) const {
     rr = rrNew;
     for (size_t i = 0; i < n; ++i) p[i] = r[i] + beta * p[i];
   }
-  const std::vector<float> xd = this->x();
+  const std::vector<float> xd = this->x(col);
   double err = 0, scale = 0;
   for (size_t i = 0; i < n; ++i) {
     err = std::max(err, std::abs(double(xd[i]) - x[i]));
@@ -281,11 +327,23 @@ void ConjugateGradient::fused_p(void *s) const {
 }
 
 void ConjugateGradient::sr_spmv_dot(void *s) const {
+  if (a_.nrhs > 1) {
+    kern::csr_spmm_dot2(int(rows()), dRow_.as<int32_t>(), dCol_.as<int32_t>(), dVal_.as<float>(),
+                        dR_.as<float>(), dW_.as<float>(), a_.nrhs, kFusedLanes, bGamma_(), bDelta_(), bScal_(0),
+                        bScal_(1), bScal_(3), bScal_(4), s);
+    return;
+  }
   kern::csr_spmv_dot2(int(rows()), dRow_.as<int32_t>(), dCol_.as<int32_t>(), dVal_.as<float>(), dR_.as<float>(),
                       dW_.as<float>(), kFusedLanes, rrp_(), pq_(), srGamma_(), srAlpha_(), srGammaPrev_(),
                       srAlphaPrev_(), s);
 }
 void ConjugateGradient::sr_update(void *s) const {
+  if (a_.nrhs > 1) {
+    kern::cg_sr_update_batch(rows(), a_.nrhs, bGamma_(), bDelta_(), np_spmv(), bScal_(3), bScal_(4),
+                             dW_.as<float>(), dR_.as<float>(), dP_.as<float>(), dS_.as<float>(), dX_.as<float>(),
+                             bScal_(0), bScal_(1), bScal_(2), s);
+    return;
+  }
   kern::cg_sr_update(rows(), rrp_(), pq_(), np_spmv(), srGammaPrev_(), srAlphaPrev_(), dW_.as<float>(),
                      dR_.as<float>(), dP_.as<float>(), dS_.as<float>(), dX_.as<float>(), srGamma_(), srAlpha_(),
                      srBeta_(), s);
@@ -297,11 +355,14 @@ std::shared_ptr<Graph> ConjugateGradient::sr_graph() const {
   auto self = shared_from_this();
   const std::string p = a_.prefix + "s_";
   // cost model as in form_graph: the SpMV with two dots is the fused form's, the update one
-  // launch with a two-slab prologue over 36 bytes per row (reads w, r, p, s, x; writes r, p, s, x)
+  // launch with a two-slab prologue over 36 bytes per row (reads w, r, p, s, x; writes r, p, s, x).
+  // With k right-hand sides the matrix (8 bytes per entry) is streamed once and every gather and
+  // every vector is k times as wide; k = 1 gives spmv_bytes().
+  const double k = double(a_.nrhs), nnz = double(A_.nnz()), n = double(rows());
   auto sd = std::make_shared<CgOp>(self, p + "spmvdot", "CgSpmvDot2", &ConjugateGradient::sr_spmv_dot, 4.5,
-                                   spmv_bytes(), 3.0e6);
+                                   8.0 * nnz + 4.0 * nnz * k + 8.0 * n * k, 3.0e6);
   auto up = std::make_shared<CgOp>(self, p + "update", "CgSrUpdate", &ConjugateGradient::sr_update, 3.5,
-                                   36.0 * double(rows()), 4.0e6);
+                                   36.0 * n * k, 4.0e6);
   auto g = std::make_shared<Graph>();
   g->start_then(sd);
   g->then(sd, up); // w, both slabs, gamma_prev and alpha_prev

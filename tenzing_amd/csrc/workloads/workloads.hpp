@@ -816,6 +816,15 @@ struct CgArgs {
   // "random": b uniform in [-1, 1), derived from seed; "zero": b = 0 (the degenerate system,
   // which must stay at x = 0 without a NaN)
   std::string rhs = "random";
+  // Right-hand sides solved side by side, 1, 2, 4 or 8: independent single-reduction recurrences
+  // on interleaved vectors (element (i, j) at i * nrhs + j) that share the matrix stream and the
+  // two launches per iteration; more than one needs form "sr". The columns are right-hand sides
+  // number rhs_first .. rhs_first + nrhs - 1 of a sequence derived from seed: number 0 is the b
+  // of a single solve, number j the same generator seeded with
+  // (seed ^ 0xC6A4A7935BD1E995) + j * 0x9E3779B97F4A7C15 (mod 2^64) and the same k / 2^23 - 1
+  // mapping. Column j is solved exactly as a single solve of right-hand side rhs_first + j: same bits.
+  int nrhs = 1;
+  int rhs_first = 0;
   std::string prefix = "cg_";
   int rank = 0, size = 1;
   Json json() const;
@@ -834,21 +843,23 @@ public:
   /// compound op
   void add_to_graph(Graph &g);
   /// x = 0, r = p = b, rr = b . b (and the rr partials that sum to it), s = 0 and the
-  /// single-reduction form's scalars 0 (its first iteration then has beta = 0); synchronous
+  /// single-reduction form's scalars 0 (its first iteration then has beta = 0); synchronous.
+  /// nrhs > 1: the same per column, b interleaved, every scalar array 0.
   void reset();
-  std::vector<float> x() const { return down(dX_); }
-  std::vector<float> r() const { return down(dR_); }
-  std::vector<float> p() const { return down(dP_); }
-  const std::vector<float> &b() const { return b_; }
-  /// r . r of the current r in every form: its partials as dot_partials_f32 writes them (the
-  /// bits of the plain and fused forms' rr slab), summed in the kernels' order
-  double rr() const;
+  /// column `col` (0 .. nrhs - 1) of the state, de-interleaved; anything else throws
+  std::vector<float> x(int col = 0) const { return down(dX_, col); }
+  std::vector<float> r(int col = 0) const { return down(dR_, col); }
+  std::vector<float> p(int col = 0) const { return down(dP_, col); }
+  const std::vector<float> &b(int col = 0) const { return b_[size_t(checked(col))]; }
+  /// r . r of the current r (of column `col`) in every form: its partials as dot_partials_f32
+  /// writes them (the bits of the plain and fused forms' rr slab), summed in the kernels' order
+  double rr(int col = 0) const;
   /// max |x - x_ref| / max |x_ref| against k iterations of CG in f64 on the host (same guards)
-  double check(int k) const;
+  double check(int k, int col = 0) const;
   /// the true residual ||b - A x||_2 / ||b||_2 of the current x, in f64 on the host (0 for b = 0).
   /// The single-reduction form's r is a recurrence of its own, so rr() no longer is this quantity
   /// by construction; this one compares the forms.
-  double residual() const;
+  double residual(int col = 0) const;
 
   // op bodies
   static constexpr int kFusedLanes = kern::kSpmvIlp + 4;
@@ -871,12 +882,13 @@ public:
   void sr_update(void *stream) const;   // beta, alpha; p, s, x, r
 
 private:
-  std::vector<float> down(const DeviceBuffer &d) const;
+  std::vector<float> down(const DeviceBuffer &d, int col) const;
+  int checked(int col) const; // col, or throws
   std::shared_ptr<Graph> form_graph(bool fused) const;
   std::shared_ptr<Graph> sr_graph() const;
   CgArgs a_;
   CsrHost A_;
-  std::vector<float> b_;
+  std::vector<std::vector<float>> b_; // one per column
   DeviceBuffer dRow_, dCol_, dVal_, dB_, dX_, dR_, dP_, dQ_;
   DeviceBuffer dS_, dW_; // the single-reduction form: s = A p by recurrence, w = A r
   // [pq partials 256 | rr partials 256 | rr | alpha | beta | the single-reduction form's gamma,
@@ -894,6 +906,12 @@ private:
   double *srGammaPrev_() const { return rr_() + 6; }
   double *srAlphaPrev_() const { return rr_() + 7; }
   double *scratch_() const { return rr_() + 8; }
+  // nrhs > 1: [delta slabs nrhs x 256 | gamma slabs nrhs x 256 | gamma, alpha, beta, gamma_prev,
+  //  alpha_prev: nrhs each]; dScal_ then only serves rr()
+  DeviceBuffer dBatch_;
+  double *bDelta_() const { return dBatch_.as<double>(); }
+  double *bGamma_() const { return bDelta_() + a_.nrhs * kern::kCgMaxPartials; }
+  double *bScal_(int i) const { return bGamma_() + a_.nrhs * kern::kCgMaxPartials + i * a_.nrhs; }
 };
 
 /// Horizontal fusion (fused_ops.cpp): the halo's self moves `dirs` and the SpMV's local product

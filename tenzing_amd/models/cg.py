@@ -7,6 +7,8 @@ pseudo-random vector. The search chooses between the plain form (8 launches) and
 (4 launches) and places the x update beside the r -> r.r -> beta -> p chain. ``form="sr"`` is
 the single-reduction (Chronopoulos-Gear) recurrence in 2 launches: an SpMV of r that also forms
 r.r and r.(A r), then one update of p, s, x and r; ``form="all"`` offers all three to the search.
+With ``nrhs`` = 2, 4 or 8 the single-reduction form solves that many right-hand sides in the same
+two launches: one matrix stream and one gather per entry serve every column.
 """
 from __future__ import annotations
 
@@ -27,12 +29,19 @@ class CgConfig:
     form: str = "choice"
     lanes: int = _tz.kernels.SPMV_ILP + 4  # csr_spmv variant of the plain form's SpMV
     rhs: str = "random"  # random: b in [-1, 1) from seed | zero: b = 0 (the degenerate system)
+    # right-hand sides solved side by side on interleaved vectors (1, 2, 4 or 8; more than one needs
+    # form="sr"): numbers rhs_first .. rhs_first + nrhs - 1 of the sequence derived from seed, of
+    # which number 0 is the b of a single solve. Column j has the bits of a single solve of
+    # right-hand side rhs_first + j; read it with x(j), r(j), p(j), b(j), rr(j), residual(j).
+    nrhs: int = 1
+    rhs_first: int = 0
     prefix: str = "cg_"
 
     def args(self, rank: int = 0, size: int = 1, device: int = -1) -> "_tz.CgArgs":
         a = _tz.CgArgs()
         a.m, a.bw, a.nnz, a.seed = self.m, self.bw, self.nnz, self.seed
         a.matrix, a.form, a.lanes, a.rhs, a.prefix = self.matrix, self.form, self.lanes, self.rhs, self.prefix
+        a.nrhs, a.rhs_first = self.nrhs, self.rhs_first
         a.rank, a.size, a.device = rank, size, device
         return a
 
