@@ -1501,6 +1501,17 @@ PYBIND11_MODULE(_tz, m) {
      py::arg("x"), py::arg("y"), py::arg("lanes") = kern::kSpmvIlp + 4, py::arg("accumulate") = false,
      py::arg("stream") = 0,
      "the direct moves (as box_move_many) and one ILP CSR SpMV in one launch, workgroups interleaved");
+  k.def("box_move_spmv_shape", [moves_from](std::vector<py::dict> ds, int n, int lanes) {
+    const std::vector<kern::MoveDesc> ms = moves_from(ds);
+    const kern::MoveSpmvShape sh = kern::box_move_spmv_shape(ms.data(), int(ms.size()), n, lanes);
+    py::dict d;
+    d["move_blocks"] = sh.move_blocks;
+    d["spmv_blocks"] = sh.spmv_blocks;
+    d["stride"] = sh.stride;
+    return d;
+  }, py::arg("moves"), py::arg("n_rows"), py::arg("lanes") = kern::kSpmvIlp + 4,
+     "the grid box_move_spmv would launch: move and SpMV workgroup counts and the interleave stride "
+     "(no GPU needed)");
   k.def("move_kinds", [moves_from](std::vector<py::dict> ds) {
     const std::vector<kern::MoveDesc> ms = moves_from(ds);
     return kern::move_kinds(ms.data(), int(ms.size()));

@@ -541,21 +541,51 @@ void launch_move_spmv(const dim3 &g, hipStream_t s, const DevBatch &b, const Spm
                        dim3(kThreads), 0, s, b, sp);
   });
 }
-} // namespace
 
-void box_move_spmv(const MoveDesc *moves, int n, const SpmvJob &job, void *stream) {
+// the moves' batch as box_move_spmv launches it (one item in flight, BoxTuning::move_items per lane)
+DevBatch move_spmv_batch(const MoveDesc *moves, int n) {
   if (n > kMaxBoxes) throw std::runtime_error("box_move_spmv: too many boxes");
-  if (job.nRows < 0 || (job.nRows > 0 && (!job.rowPtr || !job.y)))
-    throw std::runtime_error("box_move_spmv: bad SpMV job");
-  int W = 0;
-  void (*launch)(const dim3 &, hipStream_t, const DevBatch &, const SpmvDev &) = nullptr;
-  dispatch_ilp(job.lanes, "box_move_spmv: lanes must be kSpmvIlp + 1, 2 or 4", [&](auto w, auto k) {
-    W = decltype(w)::value;
-    launch = &launch_move_spmv<decltype(w)::value, decltype(k)::value>;
-  });
   std::vector<int> keep;
   const int items = std::max(1, box_tuning().move_items);
-  const DevBatch b = n > 0 ? make_move_batch(moves, n, keep, 0, items) : DevBatch{};
+  return n > 0 ? make_move_batch(moves, n, keep, 0, items) : DevBatch{};
+}
+
+// lanes per row of the ILP kernel `lanes` names (throws unless kSpmvIlp + 1, 2 or 4)
+int ilp_width(int lanes) {
+  int W = 0;
+  dispatch_ilp(lanes, "box_move_spmv: lanes must be kSpmvIlp + 1, 2 or 4",
+               [&](auto w, auto) { W = decltype(w)::value; });
+  return W;
+}
+} // namespace
+
+MoveSpmvShape box_move_spmv_shape(uint32_t moveBlocks, int nRows, int lanes) {
+  if (nRows < 0) throw std::runtime_error("box_move_spmv: bad SpMV job");
+  MoveSpmvShape sh;
+  sh.move_blocks = moveBlocks;
+  sh.spmv_blocks = uint32_t((int64_t(nRows) * ilp_width(lanes) + kThreads - 1) / kThreads);
+  const uint64_t all = uint64_t(sh.move_blocks) + sh.spmv_blocks;
+  if (all >= (uint64_t(1) << 31)) throw std::runtime_error("box_move_spmv: grid too large");
+  // an odd stride: the dispatcher deals workgroup b to XCD b % 8, so an even stride would put
+  // every SpMV workgroup on the same XCD (a stride of 8: all on XCD 0, 61 instead of 50 us)
+  sh.stride = sh.spmv_blocks ? uint32_t(all / sh.spmv_blocks) : uint32_t(all + 1);
+  if (sh.spmv_blocks && sh.stride % 2 == 0) sh.stride -= 1;
+  return sh;
+}
+
+MoveSpmvShape box_move_spmv_shape(const MoveDesc *moves, int n, int nRows, int lanes) {
+  return box_move_spmv_shape(total_blocks(move_spmv_batch(moves, n)), nRows, lanes);
+}
+
+void box_move_spmv(const MoveDesc *moves, int n, const SpmvJob &job, void *stream) {
+  if (job.nRows < 0 || (job.nRows > 0 && (!job.rowPtr || !job.y)))
+    throw std::runtime_error("box_move_spmv: bad SpMV job");
+  void (*launch)(const dim3 &, hipStream_t, const DevBatch &, const SpmvDev &) = nullptr;
+  dispatch_ilp(job.lanes, "box_move_spmv: lanes must be kSpmvIlp + 1, 2 or 4", [&](auto w, auto k) {
+    launch = &launch_move_spmv<decltype(w)::value, decltype(k)::value>;
+  });
+  const DevBatch b = move_spmv_batch(moves, n);
+  const MoveSpmvShape sh = box_move_spmv_shape(total_blocks(b), job.nRows, job.lanes);
   SpmvDev sp{};
   sp.rowPtr = job.rowPtr;
   sp.colInd = job.colInd;
@@ -564,15 +594,11 @@ void box_move_spmv(const MoveDesc *moves, int n, const SpmvJob &job, void *strea
   sp.y = job.y;
   sp.nRows = job.nRows;
   sp.accumulate = job.accumulate ? 1 : 0;
-  sp.nBlocks = uint32_t((int64_t(job.nRows) * W + kThreads - 1) / kThreads);
-  const uint64_t all = uint64_t(total_blocks(b)) + sp.nBlocks;
+  sp.nBlocks = sh.spmv_blocks;
+  sp.stride = sh.stride;
+  const uint32_t all = sh.move_blocks + sh.spmv_blocks;
   if (all == 0) return;
-  if (all >= (uint64_t(1) << 31)) throw std::runtime_error("box_move_spmv: grid too large");
-  // an odd stride: the dispatcher deals workgroup b to XCD b % 8, so an even stride would put
-  // every SpMV workgroup on the same XCD (a stride of 8: all on XCD 0, 61 instead of 50 us)
-  sp.stride = sp.nBlocks ? uint32_t(all / sp.nBlocks) : uint32_t(all + 1);
-  if (sp.nBlocks && sp.stride % 2 == 0) sp.stride -= 1;
-  launch(dim3{unsigned(all)}, static_cast<hipStream_t>(stream), b, sp);
+  launch(dim3{all}, static_cast<hipStream_t>(stream), b, sp);
   TZ_HIP_LAUNCH_CHECK();
 }
 

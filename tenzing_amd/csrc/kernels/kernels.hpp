@@ -206,6 +206,18 @@ struct SpmvJob {
 /// 150,000-row SpMV: 54.5 us one after the other, 49.2-49.8 us on two free-running streams,
 /// scripts/coexec_probe.py)
 void box_move_spmv(const MoveDesc *moves, int n, const SpmvJob &job, void *stream);
+/// The grid of a box_move_spmv launch (host only, no launch): `move_blocks` move workgroups and
+/// `spmv_blocks` = ceil(nRows * W / 256) SpMV workgroups in one grid of their sum. Workgroup b is
+/// SpMV workgroup b / stride when stride divides b and that index is below spmv_blocks, else the
+/// next move workgroup. stride = (move_blocks + spmv_blocks) / spmv_blocks, less one when even
+/// (spmv_blocks = 0: the grid size + 1, so no workgroup is an SpMV one).
+struct MoveSpmvShape {
+  uint32_t move_blocks = 0, spmv_blocks = 0, stride = 1;
+};
+/// from the move workgroup count; this is the one copy of the arithmetic, the launcher calls it
+MoveSpmvShape box_move_spmv_shape(uint32_t moveBlocks, int nRows, int lanes);
+/// from the moves themselves, batched as box_move_spmv batches them (under the current BoxTuning)
+MoveSpmvShape box_move_spmv_shape(const MoveDesc *moves, int n, int nRows, int lanes);
 /// dst[i] = src[idx[i]]
 void gather_f32(int n, const float *src, const int32_t *idx, float *dst, void *stream);
 /// one peer's part of an IPC put of the SpMV x halo: dst[i] = src[idx[off + i]], i < n, then
@@ -219,7 +231,8 @@ constexpr int kMaxPutPeers = 64;
 /// all peers' segments in one launch; `done` holds one zeroed completion counter per segment
 void gather_put_signal(const float *src, const int32_t *idx, const PutSeg *segs, int nseg,
                        unsigned int *done, void *stream);
-/// y = a + b (f32, vectorized)
+/// y = a + b (f32). The kernel reads and writes 16 bytes per access, so a, b and y must be
+/// 16-byte aligned (as copy_bytes requires): throws std::runtime_error otherwise, before any launch
 void vector_add_f32(int n, const float *a, const float *b, float *y, void *stream);
 // ---- conjugate gradient (cg_kernels.hip): f32 vectors, f64 dot accumulation, every scalar an
 // f64 in device memory. Results are deterministic (fixed partial count and summation order, no

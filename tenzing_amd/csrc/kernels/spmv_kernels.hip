@@ -304,6 +304,8 @@ void gather_put_signal(const float *src, const int32_t *idx, const PutSeg *segs,
 
 void vector_add_f32(int n, const float *a, const float *b, float *y, void *stream) {
   if (n <= 0) return;
+  if ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(y)) % 16)
+    throw std::runtime_error("vector_add_f32: pointers must be 16-byte aligned");
   hipLaunchKernelGGL(vector_add_k, dim3(grid_for(n, 4)), dim3(kThreads), 0,
                      static_cast<hipStream_t>(stream), n, a, b, y);
   TZ_HIP_LAUNCH_CHECK();

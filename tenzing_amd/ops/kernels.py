@@ -60,7 +60,9 @@ def box_unpack(grid: torch.Tensor, box: dict, buf: torch.Tensor) -> torch.Tensor
 
 def csr_spmv(row_ptr: torch.Tensor, col_ind: torch.Tensor, val: torch.Tensor, x: torch.Tensor,
              y: torch.Tensor | None = None, lanes: int = 0, accumulate: bool = False) -> torch.Tensor:
-    """y = A x (or y += A x) for CSR A with int32 indices and f32 values."""
+    """y = A x (or y += A x) for CSR A with int32 indices and f32 values. ``lanes``: W lanes per
+    row, a power of two <= 64 (0: 8); -1: the CSR-stream kernel; ``K.SPMV_ILP + W`` with W = 1, 2
+    or 4: the ILP kernel (the one the CG and fused kernels share their row body with)."""
     _check(row_ptr, torch.int32, "row_ptr")
     _check(col_ind, torch.int32, "col_ind")
     _check(val, torch.float32, "val")
@@ -73,8 +75,9 @@ def csr_spmv(row_ptr: torch.Tensor, col_ind: torch.Tensor, val: torch.Tensor, x:
     _check(y, torch.float32, "y")
     if y.numel() < n:
         raise ValueError("y too small")
-    if lanes not in (-1, 0, 1, 2, 4, 8, 16, 32, 64):
-        raise ValueError("lanes must be a power of two <= 64 (or -1: CSR-stream kernel)")
+    if lanes not in (-1, 0, 1, 2, 4, 8, 16, 32, 64, K.SPMV_ILP + 1, K.SPMV_ILP + 2, K.SPMV_ILP + 4):
+        raise ValueError("lanes must be a power of two <= 64, -1 (CSR-stream kernel) or "
+                         "SPMV_ILP + 1, 2 or 4 (ILP kernel)")
     K.csr_spmv(n, row_ptr.data_ptr(), col_ind.data_ptr(), val.data_ptr(), x.data_ptr(),
                y.data_ptr(), lanes, accumulate, _stream())
     return y
@@ -89,10 +92,14 @@ def gather(src: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
 
 
 def vector_add(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """a + b (f32). The kernel moves 16 bytes per access: a and b must start on a 16-byte
+    boundary (a slice such as ``t[1:]`` does not), else ValueError."""
     _check(a, torch.float32, "a")
     _check(b, torch.float32, "b")
     if a.numel() != b.numel():
         raise ValueError("size mismatch")
+    if a.data_ptr() % 16 or b.data_ptr() % 16:
+        raise ValueError("a and b must be 16-byte aligned")
     y = torch.empty_like(a)
     K.vector_add_f32(a.numel(), a.data_ptr(), b.data_ptr(), y.data_ptr(), _stream())
     return y
