@@ -9,6 +9,7 @@
 #include "core/deadline_claim.hpp"
 #include "core/health.hpp"
 #include "core/solve.hpp"
+#include "core/trial.hpp"
 
 #include <arpa/inet.h>
 #include <netinet/in.h>
@@ -18,6 +19,7 @@
 #include <atomic>
 #include <chrono>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <fstream>
 #include <functional>
@@ -697,6 +699,155 @@ TEST(tcp_ctrl_alltoallv_and_transport_health) {
   CHECK(domain_dead("rccl"));
   revive_domains();
   CHECK(!domain_dead("rccl") && dead_domains().empty());
+}
+
+namespace {
+/// forwards to a control plane and records the collectives made through it: 'b' barrier,
+/// 'm' allreduce_max, '?' anything else
+class CountingCtrl : public Ctrl {
+public:
+  explicit CountingCtrl(Ctrl &c) : c_(c) {}
+  std::string calls;
+  int rank() const override { return c_.rank(); }
+  int size() const override { return c_.size(); }
+  void barrier() override {
+    calls += 'b';
+    c_.barrier();
+  }
+  void bcast(std::string &d, int root) override {
+    calls += '?';
+    c_.bcast(d, root);
+  }
+  void allreduce_max(double *v, size_t n) override {
+    calls += n == 1 ? 'm' : '?';
+    c_.allreduce_max(v, n);
+  }
+  void allreduce_sum(double *v, size_t n) override {
+    calls += '?';
+    c_.allreduce_sum(v, n);
+  }
+  std::vector<std::string> allgather(const std::string &mine) override {
+    calls += '?';
+    return c_.allgather(mine);
+  }
+
+private:
+  Ctrl &c_;
+};
+} // namespace
+
+TEST(agree_keeps_the_local_reason) {
+  constexpr int N = 3;
+  std::vector<std::vector<std::string>> got(N);
+  auto err = tcp_ranks(N, [&](int r, TcpCtrl &c) {
+    got[size_t(r)].push_back(agree(c, ""));                                  // everyone passes
+    got[size_t(r)].push_back(agree(c, r == 1 ? "disk full" : ""));           // one local reason
+    got[size_t(r)].push_back(agree(c, r == 2 ? "no link" : "", "elsewhere")); // the foreign text
+    got[size_t(r)].push_back(agree(c, "rank " + std::to_string(r)));         // everyone fails
+  });
+  for (int r = 0; r < N; ++r) {
+    CHECK(err[size_t(r)].empty());
+    CHECK(got[size_t(r)].size() == 4);
+    if (got[size_t(r)].size() != 4) continue;
+    CHECK(got[size_t(r)][0].empty());
+    CHECK(got[size_t(r)][1] == (r == 1 ? "disk full" : "failed on another rank"));
+    CHECK(got[size_t(r)][2] == (r == 2 ? "no link" : "elsewhere"));
+    CHECK(got[size_t(r)][3] == "rank " + std::to_string(r));
+  }
+}
+
+TEST(agreed_trial_keeps_ranks_in_step_whatever_fails) {
+  // a sequence of trials in which nobody fails, then an exchange throws on rank 1, a verify
+  // returns a reason on rank 2, a verify throws on rank 0, and rank 1 is failed by
+  // TZ_FAIL_TRANSPORTS (its trial is named after the rank: the ranks are threads of one process
+  // and share the environment). The sequence completing at all shows that no outcome leaves the
+  // ranks in mismatched collectives; the counting control plane shows the one barrier followed
+  // by one allreduce_max per trial.
+  constexpr int N = 3, T = 5;
+  ::setenv("TZ_FAIL_TRANSPORTS", "other,sim_r1", 1);
+  CHECK(fail_simulated("sim_r1") && fail_simulated("other") && !fail_simulated("sim_r") &&
+        !fail_simulated("sim_r2") && !fail_simulated(""));
+  std::vector<std::vector<std::string>> got(N);
+  std::vector<std::string> calls(N);
+  std::vector<std::vector<int>> verified(N, std::vector<int>(T, 0));
+  auto err = tcp_ranks(N, [&](int r, TcpCtrl &tcp) {
+    CountingCtrl c(tcp);
+    for (int t = 0; t < T; ++t) {
+      const std::string name = t == 4 ? "sim_r" + std::to_string(r) : "trial" + std::to_string(t);
+      got[size_t(r)].push_back(agreed_trial(
+          c, name,
+          [&] {
+            if (t == 1 && r == 1) throw std::runtime_error("exchange broke");
+          },
+          [&]() -> std::string {
+            ++verified[size_t(r)][size_t(t)];
+            if (t == 2 && r == 2) return name + " preflight: 7 wrong cells";
+            if (t == 3 && r == 0) throw std::runtime_error("check broke");
+            return "";
+          }));
+    }
+    calls[size_t(r)] = c.calls;
+  });
+  ::unsetenv("TZ_FAIL_TRANSPORTS");
+  const int failing[T] = {-1, 1, 2, 0, 1};
+  const std::string own[T] = {"", "trial1: exchange broke", "trial2 preflight: 7 wrong cells",
+                              "trial3 check: check broke", "sim_r1: simulated failure (TZ_FAIL_TRANSPORTS)"};
+  for (int r = 0; r < N; ++r) {
+    if (!err[size_t(r)].empty()) std::fprintf(stderr, "  rank %d: %s\n", r, err[size_t(r)].c_str());
+    CHECK(err[size_t(r)].empty());
+    CHECK(calls[size_t(r)] == "bmbmbmbmbm");
+    CHECK(got[size_t(r)].size() == size_t(T));
+    for (int t = 0; t < T && got[size_t(r)].size() == size_t(T); ++t) {
+      const std::string &g = got[size_t(r)][size_t(t)];
+      if (failing[t] < 0) CHECK(g.empty());
+      else CHECK(g == (failing[t] == r ? own[t] : "failed on another rank"));
+      // verify runs exactly where the rank's own exchange did not throw
+      CHECK(verified[size_t(r)][size_t(t)] == (t == 1 && r == 1 ? 0 : 1));
+    }
+  }
+}
+
+TEST(ipc_blob_layout) {
+  // the exported blob with 64-byte opaque handles: [node identity][handles][payload]
+  constexpr size_t H = 64;
+  const std::string node = std::string("host-a|boot-1") + std::string(83, '\0');
+  const std::string other = std::string("host-b|boot-1") + std::string(83, '\0');
+  auto hnd = [&](char c) { return std::string(H, c); };
+  auto throws = [](const std::function<void()> &f, const char *what) {
+    try {
+      f();
+    } catch (const std::exception &e) {
+      return std::string(e.what()).find(what) != std::string::npos;
+    }
+    return false;
+  };
+  const std::string blob = ipc_blob::pack(node, {hnd('a'), hnd('b'), hnd('c')}, "payload!");
+  CHECK(blob.size() == node.size() + 3 * H + 8);
+  CHECK(ipc_blob::handle(blob, node, H, 0) == hnd('a'));
+  CHECK(ipc_blob::handle(blob, node, H, 1) == hnd('b'));
+  CHECK(ipc_blob::handle(blob, node, H, 2) == hnd('c'));
+  CHECK(ipc_blob::payload(blob, node.size(), H, 3) == "payload!");
+  // a blob too short for the slot (a peer that failed to export sends an empty one)
+  const std::string two = ipc_blob::pack(node, {hnd('a'), hnd('b')});
+  CHECK(ipc_blob::handle(two, node, H, 1) == hnd('b'));
+  CHECK(throws([&] { ipc_blob::handle(two, node, H, 2); }, "exported no IPC handles"));
+  CHECK(throws([&] { ipc_blob::handle(two.substr(0, two.size() - 1), node, H, 1); }, "exported no IPC handles"));
+  CHECK(throws([&] { ipc_blob::handle("", node, H, 0); }, "exported no IPC handles"));
+  CHECK(throws([&] { ipc_blob::payload(two, node.size(), H, 3); }, "exported no IPC handles"));
+  // a handle from another node is never opened
+  CHECK(throws([&] { ipc_blob::handle(blob, other, H, 0); }, "another node"));
+  // an all-zero slot is rejected, its neighbours open
+  const std::string gap = ipc_blob::pack(node, {hnd('a'), std::string(H, '\0'), hnd('c')});
+  CHECK(ipc_blob::handle(gap, node, H, 0) == hnd('a'));
+  CHECK(throws([&] { ipc_blob::handle(gap, node, H, 1); }, "no IPC handle in slot 1"));
+  CHECK(ipc_blob::handle(gap, node, H, 2) == hnd('c'));
+  // a single non-zero byte makes a handle
+  std::string one(H, '\0');
+  one[H - 1] = 1;
+  CHECK(ipc_blob::handle(ipc_blob::pack(node, {one}), node, H, 0) == one);
+  // no handles at all: the payload starts right behind the node identity
+  CHECK(ipc_blob::payload(ipc_blob::pack(node, {}, "xyz"), node.size(), H, 0) == "xyz");
+  CHECK(ipc_blob::payload(ipc_blob::pack(node, {}), node.size(), H, 0).empty());
 }
 
 TEST(ordering_domain_orders_ops_across_streams) {

@@ -256,8 +256,8 @@ HaloExchange::~HaloExchange() {
     for (void *e : kv.second.events) (void)hipEventDestroy(static_cast<hipEvent_t>(e));
     for (void *s : kv.second.streams) (void)hipStreamDestroy(static_cast<hipStream_t>(s));
   }
-  for (void *p : opened_) (void)hipIpcCloseMemHandle(p);
-  if (flags_) (void)hipFree(flags_);
+  // the peers' memory is unmapped before the members free what this rank exported
+  peers_.close();
 }
 
 int HaloExchange::coord_to_rank(int x, int y, int z) const {
@@ -426,49 +426,38 @@ void HaloExchange::setup(Ctrl *ctrl) {
       relayBuf_[i] = DeviceBuffer(most * sizeof(double), /*peerWritten=*/true);
     }
   }
-  // TZ_FAIL_TRANSPORTS=ipc,rccl,rccl_hang: simulated setup / preflight failures (tests of the
-  // fallback chain: ipc -> rccl -> host)
-  const std::string failEnv = std::getenv("TZ_FAIL_TRANSPORTS") ? std::getenv("TZ_FAIL_TRANSPORTS") : "";
-  auto simulated = [&](const std::string &what) {
-    return ("," + failEnv + ",").find("," + what + ",") != std::string::npos;
-  };
+  // fail_simulated("ipc" / "rccl" / "rccl_hang"): simulated setup / preflight failures (tests of
+  // the fallback chain: ipc -> rccl -> host)
   if (useIpc_) {
     // collective agreement: if any rank cannot map its peers, nobody uses IPC puts (with a
     // forced "ipc" transport that is an error; with "auto" RCCL remains)
     std::string why = setup_ipc(ctrl);
-    if (why.empty() && simulated("ipc")) why = "simulated failure (TZ_FAIL_TRANSPORTS)";
+    if (why.empty() && fail_simulated("ipc")) why = "simulated failure (TZ_FAIL_TRANSPORTS)";
     // agreement (and the barrier before anyone puts: every rank mapped its peers)
-    double failed = why.empty() ? 0.0 : 1.0;
-    ctrl->allreduce_max(&failed, 1);
-    ipcReady_ = failed == 0.0;
+    ipcWhy_ = agree(*ctrl, why);
+    ipcReady_ = ipcWhy_.empty();
     if (!ipcReady_) {
-      ipcWhy_ = why.empty() ? "failed on another rank" : why;
       TZ_LOG(Warn, "ipc transport unavailable: " << ipcWhy_);
       TZ_CHECK(a_.transport != "ipc", "ipc transport requested but unavailable: " << why);
     }
     if (relay_) {
       // relay routing needs more mappings (corner and edge-diagonal peers): agreed separately,
       // so a failure there costs only the relay alternative
-      double bad = relayWhy_.empty() ? 0.0 : 1.0;
-      ctrl->allreduce_max(&bad, 1);
-      relayReady_ = ipcReady_ && bad == 0.0;
+      const std::string no = agree(*ctrl, relayWhy_);
+      relayReady_ = ipcReady_ && no.empty();
       if (ipcReady_ && !relayReady_) {
-        TZ_LOG(Warn, "relay routing unavailable"
-                         << (relayWhy_.empty() ? " on another rank" : ": " + relayWhy_));
+        relayWhy_ = no;
+        TZ_LOG(Warn, "relay routing unavailable: " << relayWhy_);
         TZ_CHECK(a_.relay != "force", "relay routing forced but unavailable: " << relayWhy_);
-        if (relayWhy_.empty()) relayWhy_ = "failed on another rank";
       }
     }
   }
   if (hsOffered_ && ipcReady_) {
     // shared host memory for the PCIe share: agreed like the relay mappings (a failure costs
     // only the host-split alternative)
-    hsWhy_ = setup_hostsplit(ctrl);
-    double bad = hsWhy_.empty() ? 0.0 : 1.0;
-    ctrl->allreduce_max(&bad, 1);
-    hsReady_ = bad == 0.0;
+    hsWhy_ = agree(*ctrl, setup_hostsplit(ctrl));
+    hsReady_ = hsWhy_.empty();
     if (!hsReady_) {
-      if (hsWhy_.empty()) hsWhy_ = "failed on another rank";
       TZ_LOG(Warn, "host split unavailable: " << hsWhy_);
       TZ_CHECK(a_.hostsplit != "force", "host split forced but unavailable: " << hsWhy_);
     }
@@ -488,14 +477,13 @@ void HaloExchange::setup(Ctrl *ctrl) {
     // ranks on one GPU: RCCL refuses duplicate devices), nobody uses RCCL
     std::string why;
     try {
-      if (simulated("rccl")) TZ_THROW("simulated failure (TZ_FAIL_TRANSPORTS)");
+      if (fail_simulated("rccl")) TZ_THROW("simulated failure (TZ_FAIL_TRANSPORTS)");
       comms_ = make_rccl_comms(*ctrl, dev, n);
     } catch (const std::exception &e) {
       why = e.what();
     }
-    double failed = why.empty() ? 0.0 : 1.0;
-    ctrl->allreduce_max(&failed, 1);
-    if (failed != 0.0) drop_rccl(why.empty() ? "communicator creation failed on another rank" : why);
+    const std::string gone = agree(*ctrl, why, "communicator creation failed on another rank");
+    if (!gone.empty()) drop_rccl(gone);
   }
   init_grid();
   if (useRccl_) {
@@ -629,9 +617,7 @@ std::string HaloExchange::rccl_preflight(Ctrl &ctrl) {
   ctrl.allreduce_max(&none, 1);
   if (none != 0.0) return "";
   const double limit = preflight_limit_s(20.0);
-  const std::string failEnv = std::getenv("TZ_FAIL_TRANSPORTS") ? std::getenv("TZ_FAIL_TRANSPORTS") : "";
-  const bool simHang = ("," + failEnv + ",").find(",rccl_hang,") != std::string::npos;
-  const bool simGraph = ("," + failEnv + ",").find(",rccl_graph_schedule,") != std::string::npos;
+  const bool simHang = fail_simulated("rccl_hang"), simGraph = fail_simulated("rccl_graph_schedule");
   hipStream_t s = nullptr, side[2] = {nullptr, nullptr};
   TZ_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
   for (auto &x : side) TZ_HIP(hipStreamCreateWithFlags(&x, hipStreamNonBlocking));
@@ -687,11 +673,7 @@ std::string HaloExchange::rccl_preflight(Ctrl &ctrl) {
     why = e.what();
     drain_after_error(why);
   }
-  {
-    double failed = why.empty() ? 0.0 : 1.0;
-    ctrl.allreduce_max(&failed, 1);
-    if (failed != 0.0 && why.empty()) why = "failed on another rank";
-  }
+  why = agree(ctrl, why);
   // (2) compiled into hipGraphs the way the runtime compiles candidates (GraphBuilder, so RCCL
   // ops take the same capture path): every remote direction in one group, then one RCCL node
   // per direction with the communicators in turn, chained, over three streams of one build.

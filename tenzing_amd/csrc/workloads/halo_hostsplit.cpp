@@ -59,9 +59,8 @@ std::string HaloExchange::setup_hostsplit(Ctrl *ctrl) {
   } catch (const std::exception &e) {
     err = std::string("create: ") + e.what();
   }
-  double bad = err.empty() ? 0.0 : 1.0;
-  ctrl->allreduce_max(&bad, 1); // every inbox exists (or nobody maps any)
-  if (bad == 0) {
+  // every inbox exists (or nobody maps any)
+  if (agree(*ctrl, err).empty()) {
     try {
       hsPeer_.resize(size_t(a_.size));
       for (int i : faces)
@@ -72,13 +71,13 @@ std::string HaloExchange::setup_hostsplit(Ctrl *ctrl) {
       err = std::string("map: ") + e.what();
     }
   }
-  double bad2 = err.empty() ? 0.0 : 1.0;
-  ctrl->allreduce_max(&bad2, 1); // every peer mapped what it needs: the names can go
+  // every peer mapped what it needs (a failed create fails this one too): the names can go
+  const std::string why = agree(*ctrl, err);
   hsMine_.unlink();
-  if (bad != 0 || bad2 != 0) {
+  if (!why.empty()) {
     hsPeer_.clear();
     hsMine_ = SharedHostBuffer();
-    return err.empty() ? "failed on another rank" : err;
+    return why;
   }
   TZ_LOG(Info, "host split: " << bytes / 1048576.0 << " MiB inbox per rank in shared host memory");
   return "";
@@ -139,7 +138,7 @@ void HaloExchange::hs_wait(const std::vector<int> &dirs, const std::vector<int> 
                            void *stream) const {
   TZ_CHECK(ready() && hsReady_, "host split not set up");
   (void)faces; // the host chunks are waited for in hs_unpack, one at a time
-  kern::ipc_wait(static_cast<const unsigned long long *>(flags_), expected_.as<unsigned long long>(),
+  kern::ipc_wait(flags_.as<const unsigned long long>(), expected_.as<unsigned long long>(),
                  dirs.data(), int(dirs.size()), err_.as<int>(), ipcTimeoutS_, stream, /*lag=*/0);
 }
 
@@ -209,60 +208,24 @@ void HaloExchange::hs_unpack(const std::vector<int> &dirs, const std::vector<int
 }
 
 void HaloExchange::hostsplit_preflight(Ctrl *ctrl) {
-  // one verified exchange per offered share before the search may use it; a failure turns it
-  // off on every rank (the other transports remain)
-  std::vector<int> local, remote;
-  for (int i = 0; i < ndirs(); ++i) {
-    if (direct_[i]) local.push_back(i);
-    else if (ipc_[i]) remote.push_back(i);
-  }
+  // one verified exchange per offered share (a new value generation each) before the search may
+  // use it; a failure turns it off on every rank (the other transports remain)
   const std::vector<int> faces = relay_faces();
-  double bad = 0;
-  std::string why;
-  const double keep = ipcTimeoutS_;
-  ipcTimeoutS_ = std::min(ipcTimeoutS_, preflight_wait_s());
   int gen = 0;
   for (double f : a_.hostsplit_fracs) {
-    // a new generation of values per share: data left in a buffer or cache by the previous
-    // exchange fails the check instead of passing as current
-    init_grid(nullptr, 1 + gen++ % 3);
-    TZ_HIP(hipDeviceSynchronize());
-    ctrl->barrier();
-    if (bad == 0) {
-      try {
-        if (!local.empty()) direct_group(local, nullptr);
-        split_put_direct(remote, f, nullptr);
-        hs_put_host(faces, f, nullptr);
-        hs_wait(remote, faces, nullptr);
-        hs_unpack(remote, faces, f, nullptr);
-        TZ_HIP(hipDeviceSynchronize());
-      } catch (const std::exception &ex) {
-        bad = 1;
-        why = std::string("host split preflight: ") + ex.what();
-      }
-    }
-    ctrl->barrier();
-    if (bad == 0) {
-      try {
-        const int e = ipc_errors();
-        const uint64_t cells = check_grid();
-        if (e || cells) {
-          bad = 1;
-          why = "host split preflight (share " + std::to_string(f) + "): " + std::to_string(e) +
-                " wait timeout(s), " + std::to_string(cells) + " wrong cells";
-        }
-      } catch (const std::exception &ex) {
-        bad = 1;
-        why = std::string("host split preflight check: ") + ex.what();
-      }
-    }
-    ctrl->allreduce_max(&bad, 1);
-    if (bad != 0) break;
+    hsWhy_ = preflight_trial(
+        ctrl, "hostsplit", 1 + gen++ % 3,
+        [&](const DirLists &d) {
+          split_put_direct(d.remote, f, nullptr);
+          hs_put_host(faces, f, nullptr);
+          hs_wait(d.remote, faces, nullptr);
+          hs_unpack(d.remote, faces, f, nullptr);
+        },
+        " (share " + std::to_string(f) + ")");
+    if (!hsWhy_.empty()) break;
   }
-  ipcTimeoutS_ = keep;
-  if (bad != 0) {
+  if (!hsWhy_.empty()) {
     hsReady_ = false;
-    hsWhy_ = why.empty() ? "preflight failed on another rank" : why;
     TZ_LOG(Warn, "host split disabled: " << hsWhy_);
     reset_ipc_counters(ctrl);
     TZ_CHECK(a_.hostsplit != "force", "host split forced but " << hsWhy_);

@@ -5,6 +5,7 @@
 #include "workloads.hpp"
 
 #include "core/numeric.hpp"
+#include "core/trial.hpp"
 #include "core/util.hpp"
 #include "hip/hip_runtime.hpp"
 #include "hip/rccl_comm.hpp"

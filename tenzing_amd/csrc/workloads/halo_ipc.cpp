@@ -18,62 +18,64 @@ void HaloExchange::off_node_exchange(void *stream) const {
   for (int i : far) unpack(opp_[i], stream);
 }
 
-void HaloExchange::ipc_preflight(Ctrl *ctrl) {
-  // Complete exchanges through IPC before the search may use it: every ghost must arrive
-  // (no wait timeout) and be right on every rank. A mapping that "works" but does not deliver
-  // (or delivers wrong data) turns the transport off collectively instead of costing a wait
-  // timeout per iteration of every IPC candidate later.
-  std::vector<int> local, remote;
+HaloExchange::DirLists HaloExchange::preflight_dirs() const {
+  DirLists d;
   for (int i = 0; i < ndirs(); ++i) {
-    if (direct_[i]) local.push_back(i);
-    else if (ipc_[i]) remote.push_back(i);
+    if (direct_[i]) d.local.push_back(i);
+    else if (ipc_[i]) d.remote.push_back(i);
   }
-  double bad = 0;
-  std::string why;
-  const double keep = ipcTimeoutS_;
-  ipcTimeoutS_ = std::min(ipcTimeoutS_, preflight_wait_s());
-  // two exchanges of different value generations (the caller's, then 2): the second must
-  // deliver new data through the buffers (and past the caches) the first one used
-  for (int gen = 1; gen <= 2 && bad == 0; ++gen) {
-    if (gen > 1) {
-      // my init_grid complete before anyone puts, theirs before my check
-      init_grid(nullptr, gen);
-      ctrl->barrier();
-    }
-    try {
-      if (!local.empty()) direct_group(local, nullptr);
-      off_node_exchange(nullptr); // (directions that cross nodes: RCCL, so the check is whole)
-      put_group(remote, nullptr);
-      wait_group(remote, nullptr);
-      if (!ipcGrid_) ipc_unpack_group(remote, nullptr);
-      TZ_HIP(hipDeviceSynchronize());
-    } catch (const std::exception &ex) {
-      bad = 1;
-      why = std::string("preflight exchange: ") + ex.what();
-    }
-    // peers may still be putting into my ghosts until they have synchronized too (outside the
-    // try: every rank reaches this collective whatever failed locally)
+  return d;
+}
+
+std::string HaloExchange::preflight_trial(Ctrl *ctrl, const std::string &name, int gen,
+                                          const std::function<void(const DirLists &)> &puts,
+                                          const std::string &share) {
+  // One verified exchange (agreed_trial: one barrier, one allreduce, whatever fails locally):
+  // every ghost must arrive (no wait timeout) and be right on every rank.
+  const DirLists d = preflight_dirs();
+  const LoweredLimit lowered(ipcTimeoutS_, preflight_wait_s());
+  if (gen >= 0) {
+    // a value generation the previous exchange did not leave behind: data left in a buffer or
+    // cache fails the check instead of passing as current. My init_grid complete before anyone
+    // puts, theirs before my check
+    init_grid(nullptr, gen);
+    TZ_HIP(hipDeviceSynchronize());
     ctrl->barrier();
-    if (bad == 0) {
-      try {
+  }
+  return agreed_trial(
+      *ctrl, name,
+      [&] {
+        if (!d.local.empty()) direct_group(d.local, nullptr);
+        puts(d);
+        TZ_HIP(hipDeviceSynchronize());
+      },
+      [&] {
         const int e = ipc_errors();
         const uint64_t cells = check_grid();
-        if (e || cells) {
-          bad = 1;
-          why = "preflight exchange " + std::to_string(gen) + ": " + std::to_string(e) +
-                " wait timeout(s), " + std::to_string(cells) + " wrong cells";
-        }
-      } catch (const std::exception &ex) {
-        bad = 1;
-        why = std::string("preflight check: ") + ex.what();
-      }
-    }
-    ctrl->allreduce_max(&bad, 1);
-  }
-  ipcTimeoutS_ = keep;
-  if (bad != 0) {
+        if (!e && !cells) return std::string();
+        return name + " preflight: " + std::to_string(e) + " wait timeout(s), " + std::to_string(cells) +
+               " wrong cells" + share;
+      });
+}
+
+void HaloExchange::ipc_preflight(Ctrl *ctrl) {
+  // Complete exchanges through IPC before the search may use it. A mapping that "works" but does
+  // not deliver (or delivers wrong data) turns the transport off collectively instead of costing
+  // a wait timeout per iteration of every IPC candidate later.
+  // Two exchanges of different value generations (the caller's, initialized and followed by a
+  // barrier there, then 2): the second must deliver new data through the buffers (and past the
+  // caches) the first one used
+  std::string why;
+  for (int gen = 1; gen <= 2 && why.empty(); ++gen)
+    why = preflight_trial(ctrl, "ipc_preflight", gen == 1 ? -1 : gen, [&](const DirLists &d) {
+      off_node_exchange(nullptr); // (directions that cross nodes: RCCL, so the check is whole)
+      put_group(d.remote, nullptr);
+      wait_group(d.remote, nullptr);
+      if (!ipcGrid_) ipc_unpack_group(d.remote, nullptr);
+    });
+  if (!why.empty()) {
     ipcReady_ = false;
-    ipcWhy_ = why.empty() ? "preflight failed on another rank" : why;
+    ipcWhy_ = why;
     TZ_LOG(Warn, "ipc transport disabled: " << ipcWhy_);
     TZ_CHECK(a_.transport != "ipc", "ipc transport requested but " << why);
   }
@@ -84,60 +86,23 @@ void HaloExchange::copy_preflight(Ctrl *ctrl) {
   // The kernel-put preflight proves the mappings; the copy-engine puts take another path (the
   // runtime's peer copy, or the SDMA engines writing across the link), so each variant gets a
   // verified exchange of its own. A failure drops only that variant, on every rank.
-  std::vector<int> local, remote;
-  for (int i = 0; i < ndirs(); ++i) {
-    if (direct_[i]) local.push_back(i);
-    else if (ipc_[i]) remote.push_back(i);
-  }
-  const std::string failEnv = std::getenv("TZ_FAIL_TRANSPORTS") ? std::getenv("TZ_FAIL_TRANSPORTS") : "";
   const char *names[2] = {"memcpy_put", "sdma_put"};
-  const double keep = ipcTimeoutS_;
-  ipcTimeoutS_ = std::min(ipcTimeoutS_, preflight_wait_s());
   for (int k = 0; k < 2; ++k) {
-    double bad = 0;
-    std::string why;
-    // a generation the kernel-put preflight did not leave behind (it ended on 2, then 0)
-    init_grid(nullptr, 3 - k);
-    TZ_HIP(hipDeviceSynchronize());
-    ctrl->barrier();
-    try {
-      if (!local.empty()) direct_group(local, nullptr);
+    // generations the kernel-put preflight did not leave behind (it ended on 2, then 0)
+    copyWhy_[k] = preflight_trial(ctrl, names[k], 3 - k, [&](const DirLists &d) {
       off_node_exchange(nullptr);
-      copy_put_group(remote, nullptr, /*sdma=*/k == 1);
-      wait_group(remote, nullptr);
-      ipc_unpack_group(remote, nullptr);
-      TZ_HIP(hipDeviceSynchronize());
-    } catch (const std::exception &ex) {
-      bad = 1;
-      why = std::string(names[k]) + " preflight: " + ex.what();
-    }
-    ctrl->barrier(); // peers may still be copying into my receive buffers until they synced
-    if (bad == 0) {
-      try {
-        const int e = ipc_errors();
-        const uint64_t cells = check_grid();
-        if (e || cells)
-          why = std::string(names[k]) + " preflight: " + std::to_string(e) + " wait timeout(s), " +
-                std::to_string(cells) + " wrong cells";
-        else if (("," + failEnv + ",").find(std::string(",") + names[k] + ",") != std::string::npos)
-          why = std::string(names[k]) + " preflight: simulated failure (TZ_FAIL_TRANSPORTS)";
-        bad = why.empty() ? 0 : 1;
-      } catch (const std::exception &ex) {
-        bad = 1;
-        why = std::string(names[k]) + " preflight check: " + ex.what();
-      }
-    }
-    ctrl->allreduce_max(&bad, 1);
-    if (bad != 0) {
-      copyOk_[k] = false;
-      copyWhy_[k] = why.empty() ? "preflight failed on another rank" : why;
+      copy_put_group(d.remote, nullptr, /*sdma=*/k == 1);
+      wait_group(d.remote, nullptr);
+      ipc_unpack_group(d.remote, nullptr);
+    });
+    copyOk_[k] = copyWhy_[k].empty();
+    if (!copyOk_[k]) {
       TZ_LOG(Warn, names[k] << " variant disabled: " << copyWhy_[k]);
       // a failed exchange leaves put / wait counters out of step: every rank resets them
       // together before the next variant's exchange
       reset_ipc_counters(ctrl);
     }
   }
-  ipcTimeoutS_ = keep;
   useCopy_ = copyOk_[0] || copyOk_[1];
   init_grid();
 }
@@ -180,51 +145,16 @@ void HaloExchange::wide_put_preflight(Ctrl *ctrl) {
     return;
   }
   // then one verified exchange with the wide launches, like copy_preflight
-  std::vector<int> local, remote;
-  for (int i = 0; i < ndirs(); ++i) {
-    if (direct_[i]) local.push_back(i);
-    else if (ipc_[i]) remote.push_back(i);
-  }
-  const double keep = ipcTimeoutS_;
-  ipcTimeoutS_ = std::min(ipcTimeoutS_, preflight_wait_s());
-  double bad = 0;
-  std::string why;
-  init_grid(nullptr, 3);
-  TZ_HIP(hipDeviceSynchronize());
-  ctrl->barrier();
-  try {
-    if (!local.empty()) direct_group(local, nullptr);
+  wideWhy_ = preflight_trial(ctrl, "wide_put", 3, [&](const DirLists &d) {
     off_node_exchange(nullptr);
-    put_group(remote, nullptr, a_.wide_put_blocks);
-    wait_group(remote, nullptr);
-    if (!ipcGrid_) ipc_unpack_group(remote, nullptr);
-    TZ_HIP(hipDeviceSynchronize());
-  } catch (const std::exception &ex) {
-    bad = 1;
-    why = std::string("wide_put preflight: ") + ex.what();
-  }
-  ctrl->barrier(); // peers may still be putting into my ghosts until they synced
-  if (bad == 0) {
-    try {
-      const int e = ipc_errors();
-      const uint64_t cells = check_grid();
-      if (e || cells)
-        why = "wide_put preflight: " + std::to_string(e) + " wait timeout(s), " +
-              std::to_string(cells) + " wrong cells";
-      bad = why.empty() ? 0 : 1;
-    } catch (const std::exception &ex) {
-      bad = 1;
-      why = std::string("wide_put preflight check: ") + ex.what();
-    }
-  }
-  ctrl->allreduce_max(&bad, 1);
-  ipcTimeoutS_ = keep;
-  if (bad != 0) {
-    wideWhy_ = why.empty() ? "preflight failed on another rank" : why;
+    put_group(d.remote, nullptr, a_.wide_put_blocks);
+    wait_group(d.remote, nullptr);
+    if (!ipcGrid_) ipc_unpack_group(d.remote, nullptr);
+  });
+  widePuts_ = wideWhy_.empty();
+  if (!widePuts_) {
     TZ_LOG(Warn, "wide_put variant disabled: " << wideWhy_);
     reset_ipc_counters(ctrl);
-  } else {
-    widePuts_ = true;
   }
   init_grid();
 }
@@ -236,16 +166,13 @@ std::string HaloExchange::setup_ipc(Ctrl *ctrl) {
   TZ_CHECK(ctrl && ctrl->size() == a_.size, "ipc transport needs a control plane of size " << a_.size);
   if (const char *v = std::getenv("TZ_IPC_TIMEOUT")) ipcTimeoutS_ = std::atof(v);
   const size_t nd = size_t(ndirs());
-  const size_t H = sizeof(hipIpcMemHandle_t);
   std::string mine, err;
   try {
-    // arrival counters live in uncached memory: a remote GPU's system-scope atomics land in
-    // HBM and the local spin loads (system scope) see them without stale cache lines
+    // arrival counters (DeviceBuffer::uncached):
     // [arrivals of direction i | credits of direction i]: a receiver counts the puts it got in
     // slot i and, once it has consumed them, returns a credit to the sender's slot nd + i
     // (relay routing adds four more sections: see kSlotSets)
-    TZ_HIP(hipExtMallocWithFlags(&flags_, kSlotSets * nd * 8, hipDeviceMallocUncached));
-    TZ_HIP(hipMemset(flags_, 0, kSlotSets * nd * 8));
+    flags_ = DeviceBuffer::uncached(kSlotSets * nd * 8);
     expected_ = DeviceBuffer(nd * 8);
     TZ_HIP(hipMemset(expected_.get(), 0, nd * 8));
     sent_ = DeviceBuffer(nd * 8);
@@ -261,22 +188,17 @@ std::string HaloExchange::setup_ipc(Ctrl *ctrl) {
     TZ_HIP(hipMemset(err_.get(), 0, sizeof(int)));
     TZ_HIP(hipDeviceSynchronize());
     // exported: [flags][grid] ("grid" mode) or [flags][recv buffer of every direction]
-    auto handle_of = [&](void *p) {
-      hipIpcMemHandle_t h;
-      std::memset(&h, 0, sizeof(h));
-      if (p) TZ_HIP(hipIpcGetMemHandle(&h, p));
-      return std::string(reinterpret_cast<const char *>(&h), H);
-    };
-    mine = node_identity() + handle_of(flags_);
+    std::vector<void *> ptrs = {flags_.get()};
     if (ipcGrid_) {
-      mine += handle_of(grid());
+      ptrs.push_back(grid());
     } else {
-      for (int i = 0; i < ndirs(); ++i) mine += handle_of(ipc_[i] ? recv_[i].get() : nullptr);
+      for (int i = 0; i < ndirs(); ++i) ptrs.push_back(ipc_[i] ? recv_[i].get() : nullptr);
       // relay routing: then the relay buffer of every direction ([flags][recv x nd][relay x nd])
       if (relay_)
         for (int i = 0; i < ndirs(); ++i)
-          mine += handle_of(size_t(i) < relayBuf_.size() ? relayBuf_[i].get() : nullptr);
+          ptrs.push_back(size_t(i) < relayBuf_.size() ? relayBuf_[i].get() : nullptr);
     }
+    mine = IpcPeers::blob(ptrs);
     TZ_LOG(Info, "ipc: exported " << (ipcGrid_ ? "grid" : "receive buffers") << " and flags");
   } catch (const std::exception &e) {
     err = std::string("export: ") + e.what();
@@ -284,21 +206,6 @@ std::string HaloExchange::setup_ipc(Ctrl *ctrl) {
   }
   const std::vector<std::string> all = ctrl->allgather(mine);
   if (!err.empty()) return err;
-  const std::string me = node_identity();
-  auto open = [&](const std::string &blob, size_t k) {
-    TZ_CHECK(blob.size() >= kNodeIdBytes + (k + 1) * H, "a peer exported no IPC handles");
-    // a handle is only meaningful on the node that exported it
-    TZ_CHECK(blob.compare(0, kNodeIdBytes, me) == 0, "a peer runs on another node");
-    const char *at = blob.data() + kNodeIdBytes + k * H;
-    hipIpcMemHandle_t h;
-    std::memcpy(&h, at, H);
-    TZ_CHECK(std::any_of(at, at + H, [](char c) { return c != 0; }),
-             "a peer exported no IPC handle in slot " << k);
-    void *p = nullptr;
-    TZ_HIP(hipIpcOpenMemHandle(&p, h, hipIpcMemLazyEnablePeerAccess));
-    opened_.push_back(p);
-    return p;
-  };
   try {
     TZ_CHECK(int(all.size()) == a_.size, "allgather returned " << all.size() << " entries");
     peerGrid_.assign(size_t(a_.size), nullptr);
@@ -310,11 +217,11 @@ std::string HaloExchange::setup_ipc(Ctrl *ctrl) {
       const std::string &blob = all[size_t(q)];
       if (!peerFlags_[size_t(q)]) {
         TZ_LOG(Info, "ipc: mapping rank " << q);
-        peerFlags_[size_t(q)] = open(blob, 0);
-        if (ipcGrid_) peerGrid_[size_t(q)] = open(blob, 1);
+        peerFlags_[size_t(q)] = peers_.open(blob, 0);
+        if (ipcGrid_) peerGrid_[size_t(q)] = peers_.open(blob, 1);
       }
       // my slab facing d_i fills q's ghost side -d_i, staged in q's recv buffer of that side
-      if (!ipcGrid_) peerRecv_[size_t(i)] = open(blob, 1 + size_t(opp_[i]));
+      if (!ipcGrid_) peerRecv_[size_t(i)] = peers_.open(blob, 1 + size_t(opp_[i]));
     }
   } catch (const std::exception &e) {
     return std::string("map: ") + e.what();
@@ -325,7 +232,7 @@ std::string HaloExchange::setup_ipc(Ctrl *ctrl) {
       auto flags_of = [&](int q) {
         if (!peerFlags_[size_t(q)]) {
           TZ_LOG(Info, "ipc: mapping rank " << q << " (relay)");
-          peerFlags_[size_t(q)] = open(all[size_t(q)], 0);
+          peerFlags_[size_t(q)] = peers_.open(all[size_t(q)], 0);
         }
       };
       peerRelay_.assign(nd, nullptr);
@@ -337,8 +244,8 @@ std::string HaloExchange::setup_ipc(Ctrl *ctrl) {
         flags_of(fwdFrom_[i]);
         // my share relayed for direction i waits in the corner peer's relay buffer i; what I
         // forward for direction i goes to the final receiver's buffer of ghost side -d_i
-        peerRelay_[size_t(i)] = open(all[size_t(corner_)], 1 + nd + size_t(i));
-        peerFwdRecv_[size_t(i)] = open(all[size_t(fwdTo_[i])], 1 + size_t(opp_[i]));
+        peerRelay_[size_t(i)] = peers_.open(all[size_t(corner_)], 1 + nd + size_t(i));
+        peerFwdRecv_[size_t(i)] = peers_.open(all[size_t(fwdTo_[i])], 1 + size_t(opp_[i]));
       }
     } catch (const std::exception &e) {
       relayWhy_ = std::string("relay map: ") + e.what();
@@ -369,7 +276,7 @@ void HaloExchange::put_group(const std::vector<int> &dirs, void *stream, int max
   sig.done = done_.as<unsigned int>() + size_t(dirs.front()) * kern::kMaxBoxes;
   // flow control: put n+1 of direction i may only overwrite the peer's ghosts / receive buffer
   // after the peer has consumed put n (its credit, returned to my slot nd + i)
-  kern::ipc_wait(static_cast<const unsigned long long *>(flags_) + ndirs(), sent_.as<unsigned long long>(),
+  kern::ipc_wait(flags_.as<const unsigned long long>() + ndirs(), sent_.as<unsigned long long>(),
                  dirs.data(), int(dirs.size()), err_.as<int>(), ipcTimeoutS_, stream, /*lag=*/1);
   for (size_t k = 0; k < dirs.size(); ++k) {
     const int i = dirs[k];
@@ -423,7 +330,7 @@ void HaloExchange::copy_put_group(const std::vector<int> &dirs, void *stream, bo
     bs.push_back(pack_box(i)); // into my send buffer of direction i
     arrive.push_back(static_cast<unsigned long long *>(peerFlags_[size_t(nbr_[i])]) + i);
   }
-  kern::ipc_wait(static_cast<const unsigned long long *>(flags_) + ndirs(), sent_.as<unsigned long long>(),
+  kern::ipc_wait(flags_.as<const unsigned long long>() + ndirs(), sent_.as<unsigned long long>(),
                  dirs.data(), int(dirs.size()), err_.as<int>(), ipcTimeoutS_, stream, /*lag=*/1);
   kern::box_copy_many(grid(), bs.data(), int(bs.size()), false, stream);
   std::vector<Copy> cs;
@@ -533,7 +440,7 @@ void HaloExchange::wait_group(const std::vector<int> &dirs, void *stream) const 
   // exchange), so the credit goes back right after the wait; buffers mode returns it after
   // the unpack (ipc_unpack_group)
   const std::vector<unsigned long long *> credits = credit_ptrs(dirs);
-  kern::ipc_wait(static_cast<const unsigned long long *>(flags_), expected_.as<unsigned long long>(),
+  kern::ipc_wait(flags_.as<const unsigned long long>(), expected_.as<unsigned long long>(),
                  dirs.data(), int(dirs.size()), err_.as<int>(), ipcTimeoutS_, stream, /*lag=*/0,
                  ipcGrid_ ? credits.data() : nullptr);
 }
@@ -565,7 +472,7 @@ void HaloExchange::reset_ipc_counters(Ctrl *ctrl) {
   } catch (const std::exception &) {
   }
   ctrl->barrier();
-  TZ_HIP(hipMemset(flags_, 0, kSlotSets * size_t(ndirs()) * 8));
+  TZ_HIP(hipMemset(flags_.get(), 0, flags_.bytes()));
   TZ_HIP(hipMemset(expected_.get(), 0, expected_.bytes()));
   TZ_HIP(hipMemset(sent_.get(), 0, sent_.bytes()));
   TZ_HIP(hipMemset(relayBook_.get(), 0, relayBook_.bytes()));
@@ -649,15 +556,14 @@ double HaloExchange::link_probe(int dir, const std::string &via, int iters, Ctrl
   if ((isPut || how == "sdma" || how == "mixed") && !(ipcOk && (isPut || (useCopy_ && !ipcGrid_))))
     err = via + " unavailable";
   if (via == "rccl" && !(useRccl_ && pipe_[dir])) err = "rccl unavailable";
-  double bad = err.empty() ? 0.0 : 1.0;
-  ctrl->allreduce_max(&bad, 1);
-  if (bad != 0) {
+  const std::string no = agree(*ctrl, err, (via + " unavailable on another rank").c_str());
+  if (!no.empty()) {
     release();
-    TZ_THROW("link probe: " << (err.empty() ? via + " unavailable on another rank" : err));
+    TZ_THROW("link probe: " << no);
   }
   // a local failure travels with the collectives (every rank makes the same calls), so all
   // ranks throw together instead of leaving peers in a barrier
-  auto agree = [&](std::string &e, double *v) {
+  auto agree_or_throw = [&](std::string &e, double *v) {
     double red[2] = {v ? *v : 0.0, e.empty() ? 0.0 : 1.0};
     ctrl->allreduce_max(red, 2);
     if (v) *v = red[0];
@@ -675,7 +581,7 @@ double HaloExchange::link_probe(int dir, const std::string &via, int iters, Ctrl
   } catch (const std::exception &x) {
     e = x.what();
   }
-  agree(e, nullptr);
+  agree_or_throw(e, nullptr);
   double t = 0;
   try {
     const double t0 = wtime();
@@ -685,7 +591,7 @@ double HaloExchange::link_probe(int dir, const std::string &via, int iters, Ctrl
   } catch (const std::exception &x) {
     e = x.what();
   }
-  agree(e, &t); // (also: peers may write into my buffers until every rank got here)
+  agree_or_throw(e, &t); // (also: peers may write into my buffers until every rank got here)
   release();
   return t;
 }

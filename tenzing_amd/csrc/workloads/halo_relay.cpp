@@ -66,7 +66,7 @@ void HaloExchange::split_put_direct(const std::vector<int> &dirs, double frac, v
   std::vector<kern::BoxDesc> bs;
   kern::MoveSignal sig;
   sig.done = done_.as<unsigned int>() + size_t(dirs.front()) * kern::kMaxBoxes;
-  kern::ipc_wait(static_cast<const unsigned long long *>(flags_) + ndirs(), sent_.as<unsigned long long>(),
+  kern::ipc_wait(flags_.as<const unsigned long long>() + ndirs(), sent_.as<unsigned long long>(),
                  dirs.data(), int(dirs.size()), err_.as<int>(), ipcTimeoutS_, stream, /*lag=*/1);
   for (size_t k = 0; k < dirs.size(); ++k) {
     const int i = dirs[k];
@@ -89,7 +89,7 @@ void HaloExchange::relay_put_corner(const std::vector<int> &faces, double frac, 
   const int nd = ndirs();
   unsigned long long *book = relayBook_.as<unsigned long long>();
   // the corner peer must have forwarded my previous shares out of its relay buffers
-  kern::ipc_wait(static_cast<const unsigned long long *>(flags_) + 3 * nd, book + nd, faces.data(),
+  kern::ipc_wait(flags_.as<const unsigned long long>() + 3 * nd, book + nd, faces.data(),
                  int(faces.size()), err_.as<int>(), ipcTimeoutS_, stream, /*lag=*/1);
   std::vector<kern::BoxDesc> bs;
   kern::MoveSignal sig;
@@ -112,7 +112,7 @@ void HaloExchange::relay_forward(const std::vector<int> &faces, double frac, voi
   TZ_CHECK(!faces.empty() && faces.size() <= size_t(kern::kMaxBoxes), "bad relay face group");
   const int nd = ndirs();
   unsigned long long *book = relayBook_.as<unsigned long long>();
-  const unsigned long long *fl = static_cast<const unsigned long long *>(flags_);
+  const unsigned long long *fl = flags_.as<const unsigned long long>();
   // the origin's shares arrived in my relay buffers; the final receivers consumed what I
   // forwarded last time
   kern::ipc_wait(fl + 2 * nd, book, faces.data(), int(faces.size()), err_.as<int>(), ipcTimeoutS_,
@@ -162,7 +162,7 @@ void HaloExchange::relay_forward(const std::vector<int> &faces, double frac, voi
 void HaloExchange::relay_wait(const std::vector<int> &dirs, const std::vector<int> &faces,
                               void *stream) const {
   TZ_CHECK(ready() && relayReady_, "relay routing not set up");
-  const unsigned long long *fl = static_cast<const unsigned long long *>(flags_);
+  const unsigned long long *fl = flags_.as<const unsigned long long>();
   kern::ipc_wait(fl, expected_.as<unsigned long long>(), dirs.data(), int(dirs.size()), err_.as<int>(),
                  ipcTimeoutS_, stream, /*lag=*/0);
   kern::ipc_wait(fl + 4 * ndirs(), relayBook_.as<unsigned long long>() + 2 * ndirs(), faces.data(),
@@ -194,61 +194,29 @@ void HaloExchange::relay_unpack(const std::vector<int> &dirs, const std::vector<
 }
 
 void HaloExchange::relay_preflight(Ctrl *ctrl) {
-  // one verified relayed exchange per offered share before the search may use relay routing;
-  // a failure turns it off on every rank (ipc puts without relay remain)
-  std::vector<int> local, remote;
-  for (int i = 0; i < ndirs(); ++i) {
-    if (direct_[i]) local.push_back(i);
-    else if (ipc_[i]) remote.push_back(i);
-  }
+  // one verified relayed exchange per offered share (a new value generation each) before the
+  // search may use relay routing; a failure turns it off on every rank (ipc puts without relay
+  // remain)
   const std::vector<int> faces = relay_faces();
-  double bad = 0;
   std::string why;
-  const double keep = ipcTimeoutS_;
-  ipcTimeoutS_ = std::min(ipcTimeoutS_, preflight_wait_s());
   int gen = 0;
   for (double f : a_.relay_fracs) {
-    // a new generation of values per share: data left in a buffer or cache by the previous
-    // exchange fails the check instead of passing as current
-    init_grid(nullptr, 1 + gen++ % 3);
-    TZ_HIP(hipDeviceSynchronize());
-    ctrl->barrier();
-    if (bad == 0) {
-      try {
-        if (!local.empty()) direct_group(local, nullptr);
-        relay_put_direct(remote, f, nullptr);
-        relay_put_corner(faces, f, nullptr);
-        relay_forward(faces, f, nullptr);
-        relay_wait(remote, faces, nullptr);
-        relay_unpack(remote, faces, f, nullptr);
-        TZ_HIP(hipDeviceSynchronize());
-      } catch (const std::exception &ex) {
-        bad = 1;
-        why = std::string("relay preflight: ") + ex.what();
-      }
-    }
-    ctrl->barrier();
-    if (bad == 0) {
-      try {
-        const int e = ipc_errors();
-        const uint64_t cells = check_grid();
-        if (e || cells) {
-          bad = 1;
-          why = "relay preflight (share " + std::to_string(f) + "): " + std::to_string(e) +
-                " wait timeout(s), " + std::to_string(cells) + " wrong cells";
-        }
-      } catch (const std::exception &ex) {
-        bad = 1;
-        why = std::string("relay preflight check: ") + ex.what();
-      }
-    }
-    ctrl->allreduce_max(&bad, 1);
-    if (bad != 0) break;
+    why = preflight_trial(
+        ctrl, "relay", 1 + gen++ % 3,
+        [&](const DirLists &d) {
+          relay_put_direct(d.remote, f, nullptr);
+          relay_put_corner(faces, f, nullptr);
+          relay_forward(faces, f, nullptr);
+          relay_wait(d.remote, faces, nullptr);
+          relay_unpack(d.remote, faces, f, nullptr);
+        },
+        " (share " + std::to_string(f) + ")");
+    if (!why.empty()) break;
   }
-  ipcTimeoutS_ = keep;
-  if (bad != 0) {
+  if (!why.empty()) {
     relayReady_ = false;
-    TZ_LOG(Warn, "relay routing disabled: " << (why.empty() ? "failed on another rank" : why));
+    relayWhy_ = why;
+    TZ_LOG(Warn, "relay routing disabled: " << why);
     reset_ipc_counters(ctrl);
     TZ_CHECK(a_.relay != "force", "relay routing forced but " << why);
   }

@@ -15,6 +15,7 @@
 #include <cstring>
 #include <thread>
 
+#include "core/trial.hpp"
 #include "core/util.hpp"
 #include "hip/hip_runtime.hpp"
 
@@ -24,11 +25,10 @@ namespace tz {
 
 namespace {
 // wait for `e` for at most `limit_s` (polling; hipEventSynchronize has no bound): false if it did
-// not complete in time. TZ_FAIL_TRANSPORTS containing "link_matrix_stall" (tests) treats every
-// wait as one that never completes.
+// not complete in time. fail_simulated("link_matrix_stall") (tests) treats every wait as one that
+// never completes.
 bool wait_event_bounded(hipEvent_t e, double limit_s) {
-  const char *f = std::getenv("TZ_FAIL_TRANSPORTS");
-  const bool stall = f && (std::string(",") + f + ",").find(",link_matrix_stall,") != std::string::npos;
+  const bool stall = fail_simulated("link_matrix_stall");
   const double end = wtime() + limit_s;
   for (;;) {
     const hipError_t q = stall ? hipErrorNotReady : hipEventQuery(e);
@@ -56,7 +56,6 @@ LinkMatrix link_matrix(Ctrl &ctrl, size_t bytes, int iters, double wait_limit_s)
     out.why = "one rank: no pairs";
     return out;
   }
-  const size_t H = sizeof(hipIpcMemHandle_t);
   // Every rank makes the same control-plane calls whatever fails locally; failures are agreed.
   std::string err, mine;
   DeviceBuffer src, dst, done, flag;
@@ -69,45 +68,26 @@ LinkMatrix link_matrix(Ctrl &ctrl, size_t bytes, int iters, double wait_limit_s)
     flag = DeviceBuffer(sizeof(unsigned long long));
     TZ_HIP(hipMemset(flag.get(), 0, flag.bytes()));
     TZ_HIP(hipDeviceSynchronize());
-    hipIpcMemHandle_t h;
-    std::memset(&h, 0, sizeof(h));
-    TZ_HIP(hipIpcGetMemHandle(&h, dst.get()));
-    mine = node_identity() + std::string(reinterpret_cast<const char *>(&h), H);
+    mine = IpcPeers::blob({dst.get()});
   } catch (const std::exception &e) {
     err = std::string("export: ") + e.what();
     mine.clear();
   }
   const std::vector<std::string> all = ctrl.allgather(mine);
   std::vector<void *> peer(size_t(P), nullptr);
-  auto close_all = [&] {
-    for (void *&p : peer)
-      if (p) {
-        (void)hipIpcCloseMemHandle(p);
-        p = nullptr;
-      }
-  };
+  IpcPeers peers; // owns the mappings in `peer`
   if (err.empty()) {
     try {
-      const std::string me = node_identity();
-      for (int q = 0; q < P; ++q) {
-        if (q == R) continue;
-        const std::string &blob = all[size_t(q)];
-        TZ_CHECK(blob.size() == kNodeIdBytes + H, "rank " << q << " exported no handle");
-        TZ_CHECK(blob.compare(0, kNodeIdBytes, me) == 0, "rank " << q << " runs on another node");
-        hipIpcMemHandle_t h;
-        std::memcpy(&h, blob.data() + kNodeIdBytes, H);
-        TZ_HIP(hipIpcOpenMemHandle(&peer[size_t(q)], h, hipIpcMemLazyEnablePeerAccess));
-      }
+      for (int q = 0; q < P; ++q)
+        if (q != R) peer[size_t(q)] = peers.open(all[size_t(q)], 0);
     } catch (const std::exception &e) {
       err = std::string("map: ") + e.what();
     }
   }
-  double bad = err.empty() ? 0.0 : 1.0;
-  ctrl.allreduce_max(&bad, 1);
-  if (bad != 0.0) {
-    close_all();
+  out.why = agree(ctrl, err);
+  if (!out.why.empty()) {
+    peers.close();
     ctrl.barrier();
-    out.why = err.empty() ? "failed on another rank" : err;
     return out;
   }
   hipStream_t s = nullptr;
@@ -180,11 +160,12 @@ LinkMatrix link_matrix(Ctrl &ctrl, size_t bytes, int iters, double wait_limit_s)
     dst.leak();
     done.leak();
     flag.leak();
+    peers.leak();
   } else {
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
     if (s) (void)hipStreamDestroy(s);
-    close_all();
+    peers.close();
   }
   std::string enc(reinterpret_cast<const char *>(row.data()), row.size() * sizeof(double));
   const std::vector<std::string> rows = ctrl.allgather(err.empty() ? enc : std::string());
@@ -198,9 +179,7 @@ LinkMatrix link_matrix(Ctrl &ctrl, size_t bytes, int iters, double wait_limit_s)
       out.sdma[size_t(r)][size_t(q)] = v[size_t(P + q)];
     }
   }
-  double failed = err.empty() ? 0.0 : 1.0;
-  ctrl.allreduce_max(&failed, 1);
-  if (failed != 0.0) out.why = err.empty() ? "probe failed on another rank" : err;
+  out.why = agree(ctrl, err, "probe failed on another rank");
   return out;
 }
 

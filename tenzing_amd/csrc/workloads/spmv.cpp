@@ -1,6 +1,7 @@
 #include "workloads.hpp"
 #include "core/solve.hpp"
 
+#include "core/trial.hpp"
 #include "core/util.hpp"
 #include "hip/hip_runtime.hpp"
 #include "hip/rccl_comm.hpp"
@@ -563,8 +564,8 @@ DistSpmv::DistSpmv(SpmvArgs a, Ctrl *ctrl) : a_(std::move(a)) {
 }
 
 DistSpmv::~DistSpmv() {
-  for (void *p : opened_) (void)hipIpcCloseMemHandle(p);
-  if (flags_) (void)hipFree(flags_);
+  // the peers' memory is unmapped before the members free what this rank exported
+  peers_.close();
 }
 
 std::string DistSpmv::transport() const {
@@ -609,12 +610,10 @@ void DistSpmv::setup(Ctrl *ctrl) {
     // IPC first (collective agreement, preflight), then RCCL with the same collective fallback
     // as the halo: several ranks on one GPU (loopback) have no RCCL
     if (useIpc_) {
-      const std::string why = setup_ipc(ctrl);
-      double failed = why.empty() ? 0.0 : 1.0;
-      ctrl->allreduce_max(&failed, 1);
-      ipcReady_ = failed == 0.0;
+      const std::string why = agree(*ctrl, setup_ipc(ctrl));
+      ipcReady_ = why.empty();
       if (!ipcReady_) {
-        TZ_LOG(Warn, "SpMV ipc transport unavailable" << (why.empty() ? " on another rank" : ": " + why));
+        TZ_LOG(Warn, "SpMV ipc transport unavailable: " << why);
         TZ_CHECK(a_.transport != "ipc", "SpMV ipc transport requested but unavailable: " << why);
       }
     }
@@ -633,20 +632,17 @@ void DistSpmv::setup(Ctrl *ctrl) {
         why = e.what();
         comm_.reset();
       }
-      double failed = why.empty() ? 0.0 : 1.0;
-      ctrl->allreduce_max(&failed, 1);
-      if (failed == 0.0) {
+      why = agree(*ctrl, why);
+      if (why.empty()) {
         // one verified exchange before the search may use it, bounded like the halo's
-        why = rccl_preflight_local();
-        failed = why.empty() ? 0.0 : 1.0;
-        ctrl->allreduce_max(&failed, 1);
-        if (failed != 0.0) why = "preflight: " + (why.empty() ? std::string("failed on another rank") : why);
+        why = agree(*ctrl, rccl_preflight_local());
+        if (!why.empty()) why = "preflight: " + why;
         else rccl_graph_preflight(*ctrl);
       }
-      if (failed != 0.0) {
+      if (!why.empty()) {
         if (comm_ && !comm_->aborted()) comm_->abort();
         comm_.reset();
-        TZ_LOG(Warn, "SpMV RCCL transport unavailable" << (why.empty() ? " on another rank" : ": " + why));
+        TZ_LOG(Warn, "SpMV RCCL transport unavailable: " << why);
         TZ_CHECK(a_.transport == "auto" && useIpc_ && ipcReady_,
                  "SpMV RCCL transport unavailable and no IPC fallback: " << why);
         useRccl_ = false;
@@ -747,13 +743,11 @@ void DistSpmv::spmv_remote(void *stream, bool accumulate) const {
 std::string DistSpmv::setup_ipc(Ctrl *ctrl) {
   // Collective like the halo's: every rank makes the same control-plane calls whatever fails
   // locally. Exported per rank: [flags][remote-x buffer][my recvOff_ per rank (i32)].
-  const size_t H = sizeof(hipIpcMemHandle_t);
   const size_t P = size_t(a_.size);
   std::string mine, err;
   if (const char *v = std::getenv("TZ_IPC_TIMEOUT")) ipcTimeoutS_ = std::atof(v);
   try {
-    TZ_HIP(hipExtMallocWithFlags(&flags_, std::max<size_t>(2 * P * 8, 64), hipDeviceMallocUncached));
-    TZ_HIP(hipMemset(flags_, 0, 2 * P * 8));
+    flags_ = DeviceBuffer::uncached(std::max<size_t>(2 * P * 8, 64));
     expected_ = DeviceBuffer(P * 8);
     sent_ = DeviceBuffer(P * 8);
     done_ = DeviceBuffer(size_t(kern::kMaxPutPeers) * sizeof(unsigned int));
@@ -763,20 +757,14 @@ std::string DistSpmv::setup_ipc(Ctrl *ctrl) {
     TZ_HIP(hipMemset(done_.get(), 0, done_.bytes()));
     TZ_HIP(hipMemset(err_.get(), 0, sizeof(int)));
     TZ_HIP(hipDeviceSynchronize());
-    hipIpcMemHandle_t h;
-    mine = node_identity();
-    TZ_HIP(hipIpcGetMemHandle(&h, flags_));
-    mine.append(reinterpret_cast<const char *>(&h), H);
-    TZ_HIP(hipIpcGetMemHandle(&h, dXr_.get()));
-    mine.append(reinterpret_cast<const char *>(&h), H);
-    mine.append(reinterpret_cast<const char *>(recvOff_.data()), P * sizeof(int32_t));
+    mine = IpcPeers::blob({flags_.get(), dXr_.get()},
+                          std::string(reinterpret_cast<const char *>(recvOff_.data()), P * sizeof(int32_t)));
   } catch (const std::exception &e) {
     err = std::string("export: ") + e.what();
     mine.clear();
   }
   const std::vector<std::string> all = ctrl->allgather(mine);
   if (!err.empty()) return err;
-  const std::string me = node_identity();
   try {
     TZ_CHECK(all.size() == P, "allgather returned " << all.size() << " entries");
     peerXr_.assign(P, nullptr);
@@ -785,24 +773,12 @@ std::string DistSpmv::setup_ipc(Ctrl *ctrl) {
     for (int q = 0; q < a_.size; ++q) {
       if (q == a_.rank || (sendCount_[q] == 0 && recvCount_[q] == 0)) continue;
       const std::string &blob = all[size_t(q)];
-      TZ_CHECK(blob.size() == kNodeIdBytes + 2 * H + P * sizeof(int32_t),
-               "rank " << q << " exported no IPC handles");
-      // a handle is only meaningful on the node that exported it
-      TZ_CHECK(blob.compare(0, kNodeIdBytes, me) == 0, "rank " << q << " runs on another node");
-      auto open = [&](size_t k) {
-        hipIpcMemHandle_t h;
-        std::memcpy(&h, blob.data() + kNodeIdBytes + k * H, H);
-        void *ptr = nullptr;
-        TZ_HIP(hipIpcOpenMemHandle(&ptr, h, hipIpcMemLazyEnablePeerAccess));
-        opened_.push_back(ptr);
-        return ptr;
-      };
-      peerFlags_[size_t(q)] = open(0);
+      peerFlags_[size_t(q)] = peers_.open(blob, 0);
       if (sendCount_[q] > 0) {
-        peerXr_[size_t(q)] = open(1);
-        std::memcpy(&peerRecvOff_[size_t(q)],
-                    blob.data() + kNodeIdBytes + 2 * H + size_t(a_.rank) * sizeof(int32_t),
-                    sizeof(int32_t));
+        peerXr_[size_t(q)] = peers_.open(blob, 1);
+        const std::string offs = IpcPeers::payload(blob, 2);
+        TZ_CHECK(offs.size() == P * sizeof(int32_t), "rank " << q << " exported no receive offsets");
+        std::memcpy(&peerRecvOff_[size_t(q)], offs.data() + size_t(a_.rank) * sizeof(int32_t), sizeof(int32_t));
       }
     }
   } catch (const std::exception &e) {
@@ -868,8 +844,7 @@ void DistSpmv::rccl_graph_preflight(Ctrl &ctrl) {
   // verified here; otherwise whole-schedule capture first, then child capture. No mode works:
   // RCCL exchanges stay out of hipGraphs (their candidates run eagerly). Every rank in step.
   const double limit = preflight_limit_s(20.0);
-  const std::string failEnv = std::getenv("TZ_FAIL_TRANSPORTS") ? std::getenv("TZ_FAIL_TRANSPORTS") : "";
-  const bool simGraph = ("," + failEnv + ",").find(",rccl_graph_schedule,") != std::string::npos;
+  const bool simGraph = fail_simulated("rccl_graph_schedule");
   std::vector<CaptureMode> modes;
   if (capture_mode_forced() || rccl_capture_settled()) modes = {rccl_capture_mode()};
   else modes = {CaptureMode::Schedule, CaptureMode::Child};
@@ -977,44 +952,30 @@ void DistSpmv::rccl_graph_preflight(Ctrl &ctrl) {
 
 void DistSpmv::ipc_preflight(Ctrl *ctrl) {
   // one complete put -> wait -> release round whose arrivals are checked value by value; any
-  // failure turns IPC off for every rank
-  double bad = 0;
-  std::string why;
-  const double keep = ipcTimeoutS_;
-  ipcTimeoutS_ = std::min(ipcTimeoutS_, 3.0);
-  try {
-    put(nullptr);
-    wait_puts(nullptr);
-    TZ_HIP(hipDeviceSynchronize());
-  } catch (const std::exception &e) {
-    bad = 1;
-    why = std::string("preflight: ") + e.what();
-  }
-  ctrl->barrier(); // outside the try: every rank reaches it
-  if (bad == 0) {
-    try {
-      const int e = ipc_errors();
-      std::vector<float> xr(remoteCols_.size());
-      if (!xr.empty()) dXr_.download(xr.data(), xr.size() * 4);
-      size_t wrong = 0;
-      for (size_t i = 0; i < xr.size(); ++i) wrong += xr[i] != x_value(remoteCols_[i]);
-      if (e || wrong) {
-        bad = 1;
-        why = "preflight: " + std::to_string(e) + " wait timeout(s), " + std::to_string(wrong) +
-              " wrong remote x entries";
-      }
-      release(nullptr);
-      TZ_HIP(hipDeviceSynchronize());
-    } catch (const std::exception &ex) {
-      bad = 1;
-      why = std::string("preflight check: ") + ex.what();
-    }
-  }
-  ipcTimeoutS_ = keep;
-  ctrl->allreduce_max(&bad, 1);
-  if (bad != 0) {
+  // failure turns IPC off for every rank (the caller synchronized and barriered before)
+  const LoweredLimit lowered(ipcTimeoutS_, 3.0);
+  const std::string why = agreed_trial(
+      *ctrl, "spmv_ipc",
+      [&] {
+        put(nullptr);
+        wait_puts(nullptr);
+        TZ_HIP(hipDeviceSynchronize());
+      },
+      [&] {
+        const int e = ipc_errors();
+        std::vector<float> xr(remoteCols_.size());
+        if (!xr.empty()) dXr_.download(xr.data(), xr.size() * 4);
+        size_t wrong = 0;
+        for (size_t i = 0; i < xr.size(); ++i) wrong += xr[i] != x_value(remoteCols_[i]);
+        release(nullptr);
+        TZ_HIP(hipDeviceSynchronize());
+        if (!e && !wrong) return std::string();
+        return "spmv_ipc preflight: " + std::to_string(e) + " wait timeout(s), " + std::to_string(wrong) +
+               " wrong remote x entries";
+      });
+  if (!why.empty()) {
     ipcReady_ = false;
-    TZ_LOG(Warn, "SpMV ipc transport disabled: " << (why.empty() ? "failed on another rank" : why));
+    TZ_LOG(Warn, "SpMV ipc transport disabled: " << why);
     TZ_CHECK(a_.transport != "ipc", "SpMV ipc transport requested but " << why);
   }
   ctrl->barrier();
@@ -1039,7 +1000,7 @@ void DistSpmv::put(void *stream) const {
   if (segs.empty()) return;
   // flow control: my put n+1 may overwrite q's remote-x entries only after q's remote product
   // of put n returned the credit (to my slot size + q)
-  kern::ipc_wait(static_cast<const unsigned long long *>(flags_) + a_.size, sent_.as<unsigned long long>(),
+  kern::ipc_wait(flags_.as<const unsigned long long>() + a_.size, sent_.as<unsigned long long>(),
                  to.data(), int(to.size()), err_.as<int>(), ipcTimeoutS_, stream, /*lag=*/1);
   kern::gather_put_signal(dX_.as<float>(), dSendIdx_.as<int32_t>(), segs.data(), int(segs.size()),
                           done_.as<unsigned int>(), stream);
@@ -1050,7 +1011,7 @@ void DistSpmv::wait_puts(void *stream) const {
   std::vector<int> from;
   for (int q = 0; q < a_.size; ++q)
     if (q != a_.rank && recvCount_[q] > 0) from.push_back(q);
-  kern::ipc_wait(static_cast<const unsigned long long *>(flags_), expected_.as<unsigned long long>(),
+  kern::ipc_wait(flags_.as<const unsigned long long>(), expected_.as<unsigned long long>(),
                  from.data(), int(from.size()), err_.as<int>(), ipcTimeoutS_, stream, /*lag=*/0);
 }
 

@@ -26,7 +26,9 @@
 #include "core/graph.hpp"
 #include "kernels/kernels.hpp"
 
+#include <algorithm>
 #include <array>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -43,6 +45,20 @@ class RocsparseCsr;
 /// exchange of a preflight's size takes milliseconds)
 double preflight_limit_s(double dflt);
 
+/// lowers a wait limit to at most `limit` for a scope (a preflight's waits give up early) and
+/// restores it on every exit path
+class LoweredLimit {
+public:
+  LoweredLimit(double &v, double limit) : v_(v), keep_(v) { v_ = std::min(v_, limit); }
+  ~LoweredLimit() { v_ = keep_; }
+  LoweredLimit(const LoweredLimit &) = delete;
+  LoweredLimit &operator=(const LoweredLimit &) = delete;
+
+private:
+  double &v_;
+  const double keep_;
+};
+
 /// hipMalloc'd memory (RAII)
 class DeviceBuffer {
 public:
@@ -54,6 +70,9 @@ public:
   /// coherent with other agents at dispatch boundaries whose fences the device-side arrival
   /// waits bypass).
   DeviceBuffer(size_t bytes, bool peerWritten);
+  /// uncached memory, zeroed: counters that other GPUs update with system-scope atomics (they
+  /// land in HBM, and the local system-scope spin loads see them without stale cache lines)
+  static DeviceBuffer uncached(size_t bytes);
   ~DeviceBuffer();
   DeviceBuffer(DeviceBuffer &&o) noexcept : p_(o.p_), bytes_(o.bytes_) {
     o.p_ = nullptr;
@@ -166,6 +185,36 @@ private:
 /// handle from another node must never be opened.
 constexpr size_t kNodeIdBytes = 96;
 std::string node_identity();
+
+/// The peers' memory this rank mapped over IPC, and the blob a rank exports for that (layout:
+/// core/trial.hpp, ipc_blob). Owns the mappings: close() (also the destructor) unmaps them all,
+/// which must happen before the peers free what they exported.
+class IpcPeers {
+public:
+  IpcPeers() = default;
+  ~IpcPeers() { close(); }
+  IpcPeers(IpcPeers &&o) noexcept { opened_.swap(o.opened_); }
+  IpcPeers &operator=(IpcPeers &&o) noexcept {
+    if (this != &o) {
+      close();
+      opened_.swap(o.opened_);
+    }
+    return *this;
+  }
+  /// node_identity(), one handle per pointer (all-zero for a null pointer), then `payload`
+  static std::string blob(const std::vector<void *> &ptrs, const std::string &payload = "");
+  /// map handle `slot` of a peer's blob: the blob must hold the slot, come from this node and
+  /// the handle must not be all-zero (throws otherwise)
+  void *open(const std::string &blob, size_t slot);
+  /// the bytes behind a blob's `nslots` handles
+  static std::string payload(const std::string &blob, size_t nslots);
+  void close();
+  /// give the mappings up without unmapping them (a transfer may still be writing through one)
+  void leak() { opened_.clear(); }
+
+private:
+  std::vector<void *> opened_;
+};
 
 /// All-pairs link probe (link_matrix.cpp): put[r][q] / sdma[r][q] = GB/s rank r moved into rank
 /// q's IPC-mapped buffer by the halo's kernel put / the SDMA engines, every rank sending at once
@@ -521,7 +570,20 @@ private:
   DeviceBuffer hsBook_;
   void check_pipelined(int i) const;
   std::string setup_ipc(Ctrl *ctrl); // "" on success, else why IPC cannot be used
-  void ipc_preflight(Ctrl *ctrl);    // one verified exchange; disables IPC collectively on failure
+  void ipc_preflight(Ctrl *ctrl);    // two verified exchanges; disables IPC collectively on failure
+  /// the self-neighbour directions and the IPC directions, as every preflight exchanges them
+  struct DirLists {
+    std::vector<int> local, remote;
+  };
+  DirLists preflight_dirs() const;
+  /// One verified exchange of a transport preflight, collective (core/trial.hpp: agreed_trial
+  /// under the name `name`, with the arrival waits' limit lowered): the grid initialized to value
+  /// generation `gen` on every rank (gen < 0: the caller did that, barrier included), the self
+  /// moves, `puts`, then the wait timeouts and every ghost cell checked. "" when every rank
+  /// passed, else why not (`share` appended to a failed check's reason)
+  std::string preflight_trial(Ctrl *ctrl, const std::string &name, int gen,
+                              const std::function<void(const DirLists &)> &puts,
+                              const std::string &share = "");
   /// verified RCCL exchanges before the search may use RCCL: every direction on its own (each
   /// communicator in turn) eagerly, then one fused group compiled into a hipGraph, each under a
   /// bounded wait (a hang aborts the communicators instead of blocking). "" on success
@@ -586,7 +648,7 @@ private:
   // ipc transport state
   // counters per direction, uncached and IPC-exported, in kSlotSets sections of ndirs():
   // arrivals | credits | relay arrivals | relay credits | forwarded arrivals | forward credits
-  void *flags_ = nullptr;
+  DeviceBuffer flags_;
   static constexpr int kSlotSets = 6;
   DeviceBuffer expected_, done_, err_;
   DeviceBuffer sent_; // per direction: puts issued so far (credit wait bookkeeping)
@@ -623,7 +685,7 @@ private:
   std::vector<char> offNode_;
   std::vector<void *> peerGrid_, peerFlags_; // per rank (nullptr: not a neighbour / self)
   std::vector<void *> peerRecv_;             // per direction: the receiver's buffer ("buffers")
-  std::vector<void *> opened_;               // IPC mappings to close
+  IpcPeers peers_;                           // owns the IPC mappings above
   double ipcTimeoutS_ = 10.0;                // arrival wait limit (env TZ_IPC_TIMEOUT)
   DeviceBuffer grid_;
   std::vector<DeviceBuffer> send_, recv_;
@@ -779,9 +841,10 @@ private:
   bool useRccl_ = false, useIpc_ = false, ipcReady_ = false;
   bool rcclGraphOk_ = true;
   std::string rcclCaptureNote_;
-  void *flags_ = nullptr; // [arrivals from rank q | credits from rank q] (uncached, exported)
+  DeviceBuffer flags_; // [arrivals from rank q | credits from rank q] (uncached, exported)
   DeviceBuffer expected_, sent_, done_, err_;
-  std::vector<void *> peerXr_, peerFlags_, opened_;
+  std::vector<void *> peerXr_, peerFlags_;
+  IpcPeers peers_; // owns those mappings
   std::vector<int32_t> peerRecvOff_; // where my segment starts in peer q's remote-x buffer
   double ipcTimeoutS_ = 10.0;
   std::shared_ptr<const Graph> inner_;

@@ -13,6 +13,7 @@
 #include <cstdlib>
 #include <fstream>
 
+#include "core/trial.hpp"
 #include "core/util.hpp"
 #include "hip/hip_runtime.hpp"
 
@@ -28,6 +29,14 @@ DeviceBuffer::DeviceBuffer(size_t bytes, bool peerWritten) : bytes_(bytes) {
   if (!bytes) return;
   if (peerWritten) TZ_HIP(hipExtMallocWithFlags(&p_, bytes, hipDeviceMallocFinegrained));
   else TZ_HIP(hipMalloc(&p_, bytes));
+}
+
+DeviceBuffer DeviceBuffer::uncached(size_t bytes) {
+  DeviceBuffer b;
+  TZ_HIP(hipExtMallocWithFlags(&b.p_, bytes, hipDeviceMallocUncached));
+  b.bytes_ = bytes;
+  TZ_HIP(hipMemset(b.p_, 0, bytes));
+  return b;
 }
 
 double preflight_limit_s(double dflt) {
@@ -137,6 +146,35 @@ std::string node_identity() {
   id += "|" + boot;
   id.resize(kNodeIdBytes, '\0');
   return id;
+}
+
+std::string IpcPeers::blob(const std::vector<void *> &ptrs, const std::string &payload) {
+  std::vector<std::string> handles;
+  for (void *p : ptrs) {
+    hipIpcMemHandle_t h;
+    std::memset(&h, 0, sizeof(h));
+    if (p) TZ_HIP(hipIpcGetMemHandle(&h, p));
+    handles.emplace_back(reinterpret_cast<const char *>(&h), sizeof(h));
+  }
+  return ipc_blob::pack(node_identity(), handles, payload);
+}
+
+void *IpcPeers::open(const std::string &blob, size_t slot) {
+  hipIpcMemHandle_t h;
+  std::memcpy(&h, ipc_blob::handle(blob, node_identity(), sizeof(h), slot).data(), sizeof(h));
+  void *p = nullptr;
+  TZ_HIP(hipIpcOpenMemHandle(&p, h, hipIpcMemLazyEnablePeerAccess));
+  opened_.push_back(p);
+  return p;
+}
+
+std::string IpcPeers::payload(const std::string &blob, size_t nslots) {
+  return ipc_blob::payload(blob, kNodeIdBytes, sizeof(hipIpcMemHandle_t), nslots);
+}
+
+void IpcPeers::close() {
+  for (void *p : opened_) (void)hipIpcCloseMemHandle(p); // teardown: nothing useful to do with an error
+  opened_.clear();
 }
 
 void EmptyKernelOp::launch(void *stream, Executor &) const { kern::empty(stream); }

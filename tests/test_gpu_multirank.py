@@ -482,6 +482,23 @@ def test_copy_preflight_failure_drops_only_that_variant_loopback(gpu):
             assert run["bad1"] == run["bad2"] == run["bad3"] == 0 and run["err"] == 0, run
 
 
+def test_wide_put_preflight_failure_drops_only_that_variant_loopback(gpu):
+    """the wide kernel put fails its own verified preflight (simulated: a verified exchange is
+    counted as failed on the host): every rank drops that variant with the reason recorded, the
+    counters are reset together, kernel puts and both copy-engine puts stay, and every schedule
+    is exact"""
+    extra = {"TZ_IPC_GRID": "0", "TZ_TEST_WIDE": "on", "TZ_FAIL_TRANSPORTS": "wide_put",
+             "TZ_TEST_FUSES": "choice", "TZ_TEST_SEEDS": "4", "TZ_TEST_NO_MCTS": "1", "TZ_TEST_N": "24"}
+    res = _launch("ipc_halo", 2, extra_env=extra)
+    for r in res:
+        ta = r["transports"]
+        assert "simulated" in ta["wide_put"], ta
+        assert ta["ipc"] == "ok" and ta["memcpy_put"] == "ok" and ta["sdma_put"] == "ok", ta
+        assert not any(o.startswith(("he_via_ipcw", "he_putw_")) for o in r["graph_ops"])
+        for run in r["runs"]:
+            assert run["bad1"] == run["bad2"] == run["bad3"] == 0 and run["err"] == 0, run
+
+
 def test_bench_rejected_finalist_loopback(gpu):
     """a finalist that fails the bench's verification (forced: TZ_BENCH_REJECT=1) is rejected
     and the next one verified and timed; the record lists the rejection"""
