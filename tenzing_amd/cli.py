@@ -59,8 +59,8 @@ def _build_workload(a, ctrl, device, setup):
         h, s, g = build_fused(hc, sc, ctrl, device, setup, horizontal=a.horizontal == "on")
         return g, {"halo": h, "spmv": s}
     if a.workload == "cg":
-        c, g = build_cg(CgConfig(m=a.cg_m, form=a.cg_form, matrix=a.cg_matrix, nrhs=a.cg_nrhs), ctrl,
-                        device, setup)
+        c, g = build_cg(CgConfig(m=a.cg_m, form=a.cg_form, matrix=a.cg_matrix, nrhs=a.cg_nrhs,
+                                 tol=a.cg_tol), ctrl, device, setup)
         return g, {"cg": c}
     if a.workload == "noop":
         # reference test/test_noop_graph.cpp: Start -> op1 -> Finish (here: `--noop-width`
@@ -115,6 +115,10 @@ def cmd_search(a) -> int:
 
         bind_local_cpus(device)
     g, wl = _build_workload(a, ctrl, device, hw)
+    if hw and "cg" in wl and a.cg_tol > 0:
+        # the search replays thousands of iterations on one state: time full iterations, not the
+        # near-empty launches of a solve that has stopped
+        wl["cg"].set_armed(False)
     if a.dump_graph and ctrl.rank == 0:
         with open(a.dump_graph, "w") as f:
             f.write(g.dump_graphviz(a.workload))
@@ -219,7 +223,8 @@ _WORKLOAD_KEYS = ("workload", "noop_width", "streams", "halo_n", "nq", "ghost", 
                   "ipc_grid", "copy_puts", "copy_engines", "move_pairs", "horizontal",
                   "stencil", "rank_grid",
                   "spmv_m", "spmv_matrix", "spmv_form", "spmv_transport", "spmv_library",
-                  "spmv_distribute", "cg_m", "cg_form", "cg_matrix", "cg_nrhs", "cg_check_iters",
+                  "spmv_distribute", "cg_m", "cg_form", "cg_matrix", "cg_nrhs", "cg_tol",
+                  "cg_max_iters", "cg_check_iters",
                   "cu_partition", "stream_priorities")
 
 
@@ -304,8 +309,11 @@ def cmd_run(a) -> int:
         wl["halo"].init_grid()
     if "spmv" in wl:
         wl["spmv"].reset_y()
+    cg_tol = "cg" in wl and w.cg_tol > 0
     if "cg" in wl:
         wl["cg"].reset()
+        if cg_tol:
+            wl["cg"].set_armed(False)  # cg_check_iters full iterations for the fixed-k check
     rt.device_sync()
     rt.prepare(seq)
     # one run before the checks; CG: exactly the iterations its host reference runs
@@ -337,12 +345,27 @@ def cmd_run(a) -> int:
         ok &= out["cg_max_rel_err"] < 1e-4
         # the true residual ||b - A x|| / ||b|| of that x: the same quantity in every form
         out["cg_residual"] = max(wl["cg"].residual(j) for j in cols)
+        if cg_tol:
+            # the solve itself: from x = 0 until every column has stopped on the device
+            from tenzing_amd.models.cg import solve
+
+            wl["cg"].reset()
+            sol = solve(wl["cg"], rt, w.cg_max_iters)
+            out["cg_tol"] = w.cg_tol
+            out["cg_iterations"] = max(sol.iterations)
+            out["cg_converged"] = all(sol.converged)
+            out["cg_residual"] = max(sol.residual)
+            ok &= out["cg_converged"]
+            wl["cg"].reset()
+            wl["cg"].set_armed(False)  # warm up and time full iterations
     rt.precompile(a.warmup)
     rt.run(a.warmup)
     rt.precompile(a.iters)  # the remainder of the unroll as one graph, compiled before timing
     rt.device_sync()
     if "cg" in wl:
         wl["cg"].reset()  # the timed iterations start from x = 0
+        if cg_tol:
+            wl["cg"].set_armed(False)
     ctrl.barrier()
     t0 = time.perf_counter()
     rt.run(a.iters)
@@ -544,6 +567,13 @@ def _parser() -> argparse.ArgumentParser:
     s.add_argument("--cg-nrhs", type=int, default=1,
                    help="cg: right-hand sides solved side by side (1, 2, 4 or 8; more than one needs "
                         "--cg-form sr): one matrix stream and one gather per entry serve all of them")
+    s.add_argument("--cg-tol", type=float, default=0.0,
+                   help="cg (needs --cg-form sr): stop each right-hand side on the device at "
+                        "r.r <= tol^2 b.b and freeze it; `search` times full iterations (the test "
+                        "disarmed), `run` also solves and reports cg_iterations, cg_converged and "
+                        "the solve's cg_residual. 0: no test, the kernels without it")
+    s.add_argument("--cg-max-iters", type=int, default=1000,
+                   help="cg with --cg-tol, `run`: iterations the solve may launch")
     s.add_argument("--cg-check-iters", type=int, default=25,
                    help="cg, `run`: iterations checked against the host's f64 CG (cg_max_rel_err)")
     s.set_defaults(fn=cmd_search)

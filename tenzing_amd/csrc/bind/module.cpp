@@ -1194,6 +1194,7 @@ PYBIND11_MODULE(_tz, m) {
       .def_readwrite("rhs", &CgArgs::rhs)
       .def_readwrite("nrhs", &CgArgs::nrhs)
       .def_readwrite("rhs_first", &CgArgs::rhs_first)
+      .def_readwrite("tol", &CgArgs::tol)
       .def_readwrite("prefix", &CgArgs::prefix)
       .def_readwrite("rank", &CgArgs::rank)
       .def_readwrite("size", &CgArgs::size)
@@ -1225,7 +1226,18 @@ PYBIND11_MODULE(_tz, m) {
              "max |x - x_ref| / max |x_ref| against k host iterations in f64")
         .def("residual", &ConjugateGradient::residual, py::arg("col") = 0,
              py::call_guard<py::gil_scoped_release>(),
-             "the true residual ||b - A x|| / ||b|| of the current x, in f64 on the host");
+             "the true residual ||b - A x|| / ||b|| of the current x, in f64 on the host")
+        .def("set_armed", &ConjugateGradient::set_armed, py::arg("armed"),
+             py::call_guard<py::gil_scoped_release>(),
+             "tol > 0: False makes every threshold -1 (the stopping kernels then always run their full "
+             "path, for searches and timing loops), True restores tol^2 b . b; reset() arms")
+        .def("armed", &ConjugateGradient::armed)
+        .def("iterations", &ConjugateGradient::iterations, py::arg("col") = 0,
+             "tol > 0: iterations column col took before it stopped, or so far (synchronous)")
+        .def("converged", &ConjugateGradient::converged, py::arg("col") = 0,
+             "tol > 0: whether column col's last update found r . r <= threshold (synchronous)")
+        .def("threshold", &ConjugateGradient::threshold, py::arg("col") = 0,
+             "tol > 0: the armed threshold tol^2 * sum b[i]^2 of column col");
   }
   m.def("read_matrix_market", [](const std::string &path) {
     CsrHost a = read_matrix_market(path);
@@ -1449,6 +1461,65 @@ PYBIND11_MODULE(_tz, m) {
   }, py::arg("n"), py::arg("k"), py::arg("partials_gamma"), py::arg("partials_delta"), py::arg("np"),
      py::arg("gamma_prev"), py::arg("alpha_prev"), py::arg("w"), py::arg("r"), py::arg("p"), py::arg("s"),
      py::arg("x"), py::arg("gamma_out"), py::arg("alpha_out"), py::arg("beta_out"), py::arg("stream") = 0);
+  k.def("csr_spmv_dot2_stop", [](int n, uintptr_t rp, uintptr_t ci, uintptr_t v, uintptr_t r, uintptr_t w,
+                                 int lanes, uintptr_t pg, uintptr_t pd, uintptr_t gOut, uintptr_t aOut,
+                                 uintptr_t gPrev, uintptr_t aPrev, uintptr_t done, uintptr_t s) {
+    kern::csr_spmv_dot2_stop(n, reinterpret_cast<const int32_t *>(rp), reinterpret_cast<const int32_t *>(ci),
+                             reinterpret_cast<const float *>(v), reinterpret_cast<const float *>(r),
+                             reinterpret_cast<float *>(w), lanes, reinterpret_cast<double *>(pg),
+                             reinterpret_cast<double *>(pd), reinterpret_cast<const double *>(gOut),
+                             reinterpret_cast<const double *>(aOut), reinterpret_cast<double *>(gPrev),
+                             reinterpret_cast<double *>(aPrev), reinterpret_cast<const int *>(done), P(s));
+  }, py::arg("n_rows"), py::arg("row_ptr"), py::arg("col_ind"), py::arg("val"), py::arg("r"), py::arg("w"),
+     py::arg("lanes"), py::arg("partials_gamma"), py::arg("partials_delta"), py::arg("gamma_out"),
+     py::arg("alpha_out"), py::arg("gamma_prev"), py::arg("alpha_prev"), py::arg("done"), py::arg("stream") = 0);
+  k.def("cg_sr_update_stop", [](int64_t n, uintptr_t pg, uintptr_t pd, int np, uintptr_t gPrev, uintptr_t aPrev,
+                                uintptr_t w, uintptr_t r, uintptr_t p, uintptr_t sv, uintptr_t x, uintptr_t gOut,
+                                uintptr_t aOut, uintptr_t bOut, uintptr_t thresh, uintptr_t done, uintptr_t iters,
+                                uintptr_t s) {
+    kern::cg_sr_update_stop(n, reinterpret_cast<const double *>(pg), reinterpret_cast<const double *>(pd), np,
+                            reinterpret_cast<const double *>(gPrev), reinterpret_cast<const double *>(aPrev),
+                            reinterpret_cast<const float *>(w), reinterpret_cast<float *>(r),
+                            reinterpret_cast<float *>(p), reinterpret_cast<float *>(sv),
+                            reinterpret_cast<float *>(x), reinterpret_cast<double *>(gOut),
+                            reinterpret_cast<double *>(aOut), reinterpret_cast<double *>(bOut),
+                            reinterpret_cast<const double *>(thresh), reinterpret_cast<int *>(done),
+                            reinterpret_cast<int64_t *>(iters), P(s));
+  }, py::arg("n"), py::arg("partials_gamma"), py::arg("partials_delta"), py::arg("np"), py::arg("gamma_prev"),
+     py::arg("alpha_prev"), py::arg("w"), py::arg("r"), py::arg("p"), py::arg("s"), py::arg("x"),
+     py::arg("gamma_out"), py::arg("alpha_out"), py::arg("beta_out"), py::arg("thresh"), py::arg("done"),
+     py::arg("iters"), py::arg("stream") = 0);
+  k.def("csr_spmm_dot2_stop", [](int n, uintptr_t rp, uintptr_t ci, uintptr_t v, uintptr_t r, uintptr_t w,
+                                 int nrhs, int lanes, uintptr_t pg, uintptr_t pd, uintptr_t gOut, uintptr_t aOut,
+                                 uintptr_t gPrev, uintptr_t aPrev, uintptr_t allDone, uintptr_t s) {
+    kern::csr_spmm_dot2_stop(n, reinterpret_cast<const int32_t *>(rp), reinterpret_cast<const int32_t *>(ci),
+                             reinterpret_cast<const float *>(v), reinterpret_cast<const float *>(r),
+                             reinterpret_cast<float *>(w), nrhs, lanes, reinterpret_cast<double *>(pg),
+                             reinterpret_cast<double *>(pd), reinterpret_cast<const double *>(gOut),
+                             reinterpret_cast<const double *>(aOut), reinterpret_cast<double *>(gPrev),
+                             reinterpret_cast<double *>(aPrev), reinterpret_cast<const int *>(allDone), P(s));
+  }, py::arg("n_rows"), py::arg("row_ptr"), py::arg("col_ind"), py::arg("val"), py::arg("r"), py::arg("w"),
+     py::arg("k"), py::arg("lanes"), py::arg("partials_gamma"), py::arg("partials_delta"), py::arg("gamma_out"),
+     py::arg("alpha_out"), py::arg("gamma_prev"), py::arg("alpha_prev"), py::arg("all_done"),
+     py::arg("stream") = 0);
+  k.def("cg_sr_update_batch_stop", [](int64_t n, int nrhs, uintptr_t pg, uintptr_t pd, int np, uintptr_t gPrev,
+                                      uintptr_t aPrev, uintptr_t w, uintptr_t r, uintptr_t p, uintptr_t sv,
+                                      uintptr_t x, uintptr_t gOut, uintptr_t aOut, uintptr_t bOut,
+                                      uintptr_t thresh, uintptr_t done, uintptr_t iters, uintptr_t allDone,
+                                      uintptr_t s) {
+    kern::cg_sr_update_batch_stop(n, nrhs, reinterpret_cast<const double *>(pg),
+                                  reinterpret_cast<const double *>(pd), np,
+                                  reinterpret_cast<const double *>(gPrev), reinterpret_cast<const double *>(aPrev),
+                                  reinterpret_cast<const float *>(w), reinterpret_cast<float *>(r),
+                                  reinterpret_cast<float *>(p), reinterpret_cast<float *>(sv),
+                                  reinterpret_cast<float *>(x), reinterpret_cast<double *>(gOut),
+                                  reinterpret_cast<double *>(aOut), reinterpret_cast<double *>(bOut),
+                                  reinterpret_cast<const double *>(thresh), reinterpret_cast<int *>(done),
+                                  reinterpret_cast<int64_t *>(iters), reinterpret_cast<int *>(allDone), P(s));
+  }, py::arg("n"), py::arg("k"), py::arg("partials_gamma"), py::arg("partials_delta"), py::arg("np"),
+     py::arg("gamma_prev"), py::arg("alpha_prev"), py::arg("w"), py::arg("r"), py::arg("p"), py::arg("s"),
+     py::arg("x"), py::arg("gamma_out"), py::arg("alpha_out"), py::arg("beta_out"), py::arg("thresh"),
+     py::arg("done"), py::arg("iters"), py::arg("all_done"), py::arg("stream") = 0);
   k.def("gather_f32", [](int n, uintptr_t src, uintptr_t idx, uintptr_t dst, uintptr_t s) {
     kern::gather_f32(n, reinterpret_cast<const float *>(src), reinterpret_cast<const int32_t *>(idx),
                      reinterpret_cast<float *>(dst), P(s));

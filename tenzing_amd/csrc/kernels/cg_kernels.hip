@@ -1,7 +1,8 @@
 // Conjugate-gradient kernels for gfx950: dot products, vector updates whose coefficient lives in
 // device memory, the fused forms (SpMV + dot, update + dot) and the single-reduction form's two
 // kernels (SpMV + two dots, one update of p, s, x and r), those two also for 2, 4 or 8 interleaved
-// right-hand sides. Not in the reference.
+// right-hand sides, and all four again with a convergence test decided on the device (*_stop).
+// Not in the reference.
 //
 // Vectors are f32; dot products accumulate in f64 (the product of two f32 values is exact in
 // f64); every scalar (rr, alpha, beta) is an f64 in device memory, so no launch argument carries
@@ -81,6 +82,11 @@ __device__ __forceinline__ double dot_quad(double acc, float4 a, float4 b) {
   acc += double(a.z) * double(b.z);
   acc += double(a.w) * double(b.w);
   return acc;
+}
+
+// v = old in the lanes whose `keep` is set
+__device__ __forceinline__ void keep_quad(float4 &v, float4 old, const bool (&keep)[4]) {
+  v.x = keep[0] ? old.x : v.x, v.y = keep[1] ? old.y : v.y, v.z = keep[2] ? old.z : v.z, v.w = keep[3] ? old.w : v.w;
 }
 
 __global__ __launch_bounds__(kThreads) void dot_partials_k(int64_t n, const float *u, const float *v,
@@ -284,6 +290,50 @@ __global__ __launch_bounds__(kSpmvThreads) void csr_spmv_dot2_k(int nRows, const
   }
 }
 
+// The stopping forms (the four kernels named *_stop_k) add a convergence test that needs no
+// hand-off inside a launch (rule 2). Every block of the update sums the same gamma slab in the
+// same order, so gamma = r . r has the same bits in every block and `gamma <= *thresh` (thresh in
+// device memory) sends the whole grid the same way: a stopped update writes no vector. Block 0
+// records the outcome in *done and the next launch reads it, as gammaOut and alphaOut travel. A
+// set flag returns every block of the SpMV before it writes, so w, both slabs and the previous
+// scalars keep what the stopped update saw; the next update forms the same gamma and stops again:
+// a stopped iteration stays stopped under any number of replays. A NaN gamma compares false and
+// never stops. Each stopping kernel repeats its parent line for line after the test (the parents
+// stay as they were compiled), and tests/test_gpu_cg_tol_kernels.py holds the two to the same bits.
+template <int W, int K>
+__global__ __launch_bounds__(kSpmvThreads) void csr_spmv_dot2_stop_k(
+    int nRows, const int32_t *__restrict__ rowPtr, const int32_t *__restrict__ colInd,
+    const float *__restrict__ val, const float *__restrict__ r, float *__restrict__ w,
+    double *__restrict__ partialsGamma, double *__restrict__ partialsDelta, const double *__restrict__ gammaOut,
+    const double *__restrict__ alphaOut, double *__restrict__ gammaPrev, double *__restrict__ alphaPrev,
+    const int *__restrict__ done) {
+  __shared__ double sh[kSpmvThreads / 64];
+  if (*done) return; // uniform over the grid
+  if (gammaOut && blockIdx.x == 0 && threadIdx.x == 0) {
+    *gammaPrev = *gammaOut;
+    *alphaPrev = *alphaOut;
+  }
+  const int lane = threadIdx.x & (W - 1);
+  const int rowsPerPass = int(gridDim.x) * (kSpmvThreads / W);
+  double accG = 0.0, accD = 0.0;
+  // whole W-lane groups leave the loop together (W divides 64)
+  for (int row = (blockIdx.x * kSpmvThreads + threadIdx.x) / W; row < nRows; row += rowsPerPass) {
+    const float sum = dev::csr_spmv_ilp_sum<W, K>(row, lane, rowPtr, colInd, val, r);
+    if (lane == 0) {
+      const double ri = double(r[row]);
+      w[row] = sum;
+      accG += ri * ri;
+      accD += ri * double(sum);
+    }
+  }
+  const double g = block_sum<kSpmvThreads / 64>(accG, sh);
+  const double d = block_sum<kSpmvThreads / 64>(accD, sh);
+  if (threadIdx.x == 0) {
+    partialsGamma[blockIdx.x] = g;
+    partialsDelta[blockIdx.x] = d;
+  }
+}
+
 // N block_sums behind one barrier, for a block whose result only leaves through one store per
 // value: the same butterfly per value, then thread i < N adds the NW wave sums of value i in wave
 // order and returns block_sum<NW>(v[i])'s bits (other threads: unspecified). sh: N * NW doubles.
@@ -354,6 +404,48 @@ __global__ __launch_bounds__(kSpmvThreads) void csr_spmm_dot2_k(int nRows, const
   else if (t < 2 * NR) partialsDelta[(t - NR) * kCgMaxPartials + blockIdx.x] = sum;
 }
 
+// csr_spmm_dot2_k that returns early only once every column has stopped (*allDone, which block 0
+// of the batched update writes). Until then a stopped column is computed again from its unchanged
+// r: the same w, the same gamma, so the update stops it again without remembering that it had.
+template <int W, int K, int NR>
+__global__ __launch_bounds__(kSpmvThreads) void csr_spmm_dot2_stop_k(
+    int nRows, const int32_t *__restrict__ rowPtr, const int32_t *__restrict__ colInd,
+    const float *__restrict__ val, const float *__restrict__ r, float *__restrict__ w,
+    double *__restrict__ partialsGamma, double *__restrict__ partialsDelta, const double *__restrict__ gammaOut,
+    const double *__restrict__ alphaOut, double *__restrict__ gammaPrev, double *__restrict__ alphaPrev,
+    const int *__restrict__ allDone) {
+  __shared__ double sh[2 * NR * (kSpmvThreads / 64)];
+  if (*allDone) return; // uniform over the grid
+  if (gammaOut && blockIdx.x == 0 && int(threadIdx.x) < NR) {
+    gammaPrev[threadIdx.x] = gammaOut[threadIdx.x];
+    alphaPrev[threadIdx.x] = alphaOut[threadIdx.x];
+  }
+  const int lane = threadIdx.x & (W - 1);
+  const int rowsPerPass = int(gridDim.x) * (kSpmvThreads / W);
+  double acc[2 * NR]; // gamma of column j at j, delta at NR + j
+#pragma unroll
+  for (int j = 0; j < 2 * NR; ++j) acc[j] = 0.0;
+  // whole W-lane groups leave the loop together (W divides 64)
+  for (int row = (blockIdx.x * kSpmvThreads + threadIdx.x) / W; row < nRows; row += rowsPerPass) {
+    float sum[NR];
+    dev::csr_spmm_ilp_sum<W, K, NR>(row, lane, rowPtr, colInd, val, r, sum);
+    if (lane == 0) {
+      float ri[NR];
+      dev::load_row<NR>(r + int64_t(row) * NR, ri);
+      dev::store_row<NR>(w + int64_t(row) * NR, sum);
+#pragma unroll
+      for (int j = 0; j < NR; ++j) {
+        acc[j] += double(ri[j]) * double(ri[j]);
+        acc[NR + j] += double(ri[j]) * double(sum[j]);
+      }
+    }
+  }
+  const double sum = block_sum_n<kSpmvThreads / 64, 2 * NR>(acc, sh);
+  const int t = threadIdx.x; // thread j writes gamma's slab j, thread NR + j delta's
+  if (t < NR) partialsGamma[t * kCgMaxPartials + blockIdx.x] = sum;
+  else if (t < 2 * NR) partialsDelta[(t - NR) * kCgMaxPartials + blockIdx.x] = sum;
+}
+
 // alpha = gamma / (delta - beta * (gamma / alphaPrev)), every division guarded. The product and
 // the difference round separately (no fma), so the bits are those of the same expression in any
 // IEEE f64 arithmetic. This file is built with -ffp-contract=fast, which disregards `#pragma
@@ -387,6 +479,61 @@ __global__ __launch_bounds__(kThreads) void cg_sr_update_k(int64_t n, const doub
     *gammaOut = gamma;
     *alphaOut = alpha;
     *betaOut = beta;
+  }
+  const float b = float(beta), a = float(alpha), na = -a;
+  const bool aw = aligned16(w), ar = aligned16(r), ap = aligned16(p), as = aligned16(s), ax = aligned16(x);
+  const int64_t nq = n / 4, stride = int64_t(gridDim.x) * kThreads;
+  for (int64_t k = int64_t(blockIdx.x) * kThreads + threadIdx.x; k < nq; k += stride) {
+    const float4 wv = load_quad(w, k, aw);
+    float4 rv = load_quad(r, k, ar), pv = load_quad(p, k, ap), sv = load_quad(s, k, as), xv = load_quad(x, k, ax);
+    pv.x = fmaf(b, pv.x, rv.x), pv.y = fmaf(b, pv.y, rv.y), pv.z = fmaf(b, pv.z, rv.z), pv.w = fmaf(b, pv.w, rv.w);
+    sv.x = fmaf(b, sv.x, wv.x), sv.y = fmaf(b, sv.y, wv.y), sv.z = fmaf(b, sv.z, wv.z), sv.w = fmaf(b, sv.w, wv.w);
+    xv.x = fmaf(a, pv.x, xv.x), xv.y = fmaf(a, pv.y, xv.y), xv.z = fmaf(a, pv.z, xv.z), xv.w = fmaf(a, pv.w, xv.w);
+    rv.x = fmaf(na, sv.x, rv.x), rv.y = fmaf(na, sv.y, rv.y), rv.z = fmaf(na, sv.z, rv.z), rv.w = fmaf(na, sv.w, rv.w);
+    store_quad(p, k, ap, pv);
+    store_quad(s, k, as, sv);
+    store_quad(x, k, ax, xv);
+    store_quad(r, k, ar, rv);
+  }
+  const int64_t t = nq * 4 + threadIdx.x;
+  if (blockIdx.x == 0 && t < n) {
+    const float rt = r[t];
+    const float pt = fmaf(b, p[t], rt), st = fmaf(b, s[t], w[t]);
+    p[t] = pt;
+    s[t] = st;
+    x[t] = fmaf(a, pt, x[t]);
+    r[t] = fmaf(na, st, rt);
+  }
+}
+
+// cg_sr_update_k with the test after the same prologue. gamma <= *thresh ends every block before
+// it touches a vector, and block 0 stores only gamma and *done = 1. Otherwise the pass is
+// cg_sr_update_k's, and block 0 also stores *done = 0 and counts the iteration in *iters; no
+// block's path depends on done or iters.
+__global__ __launch_bounds__(kThreads) void cg_sr_update_stop_k(
+    int64_t n, const double *__restrict__ partialsGamma, const double *__restrict__ partialsDelta, int np,
+    const double *__restrict__ gammaPrev, const double *__restrict__ alphaPrev, const float *w, float *r,
+    float *p, float *s, float *x, double *__restrict__ gammaOut, double *__restrict__ alphaOut,
+    double *__restrict__ betaOut, const double *__restrict__ thresh, int *__restrict__ done,
+    int64_t *__restrict__ iters) {
+  __shared__ double sh[kThreads / 64];
+  const double gamma = sum_partials<kThreads / 64>(partialsGamma, np, sh);
+  const double delta = sum_partials<kThreads / 64>(partialsDelta, np, sh);
+  const double beta = guarded_div(gamma, *gammaPrev);
+  const double alpha = sr_alpha(gamma, delta, beta, *alphaPrev);
+  if (gamma <= *thresh) { // the same bits, hence the same branch, in every block
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+      *gammaOut = gamma;
+      *done = 1;
+    }
+    return;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    *gammaOut = gamma;
+    *alphaOut = alpha;
+    *betaOut = beta;
+    *done = 0;
+    *iters += 1;
   }
   const float b = float(beta), a = float(alpha), na = -a;
   const bool aw = aligned16(w), ar = aligned16(r), ap = aligned16(p), as = aligned16(s), ax = aligned16(x);
@@ -489,6 +636,109 @@ __global__ __launch_bounds__(kThreads) void cg_sr_update_batch_k(
   // the total % 4 tail elements (NR = 2 with an odd n only)
   const int64_t t = nq * 4 + tid;
   if (blockIdx.x == 0 && t < total) {
+    const float bt = shB[t & (NR - 1)], at = shA[t & (NR - 1)];
+    const float rt = r[t];
+    const float pt = fmaf(bt, p[t], rt), st = fmaf(bt, s[t], w[t]);
+    p[t] = pt;
+    s[t] = st;
+    x[t] = fmaf(at, pt, x[t]);
+    r[t] = fmaf(-at, st, rt);
+  }
+}
+
+// cg_sr_update_batch_k with one test per column: thread j < NR also forms stop_j = gamma_j <=
+// thresh[j], the same in every block. A stopped column is frozen by a per-lane select that stores
+// back the p, s, x and r it loaded (a thread's lanes always hold the same columns); its alpha and
+// beta are not published and its iters not counted. Once every column has stopped no block passes
+// over the vectors. Block 0 stores done[j] = stop_j and *allDone = their AND.
+template <int NR>
+__global__ __launch_bounds__(kThreads) void cg_sr_update_batch_stop_k(
+    int64_t n, const double *__restrict__ partialsGamma, const double *__restrict__ partialsDelta, int np,
+    const double *__restrict__ gammaPrev, const double *__restrict__ alphaPrev, const float *w, float *r,
+    float *p, float *s, float *x, double *__restrict__ gammaOut, double *__restrict__ alphaOut,
+    double *__restrict__ betaOut, const double *__restrict__ thresh, int *__restrict__ done,
+    int64_t *__restrict__ iters, int *__restrict__ allDone) {
+  constexpr int NW = kThreads / 64;
+  __shared__ double sh[2 * NR * NW];
+  __shared__ float shB[NR], shA[NR];
+  __shared__ int shStop[NR];
+  const int tid = threadIdx.x;
+  double v[2 * NR]; // gamma of column j at j, delta at NR + j
+#pragma unroll
+  for (int j = 0; j < NR; ++j) {
+    v[j] = tid < np ? partialsGamma[j * kCgMaxPartials + tid] : 0.0;
+    v[NR + j] = tid < np ? partialsDelta[j * kCgMaxPartials + tid] : 0.0;
+  }
+#pragma unroll
+  for (int i = 0; i < 2 * NR; ++i) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v[i] += __shfl_xor(v[i], off, 64);
+  }
+  if ((tid & 63) == 0) {
+#pragma unroll
+    for (int i = 0; i < 2 * NR; ++i) sh[i * NW + (tid >> 6)] = v[i];
+  }
+  __syncthreads();
+  if (tid < NR) {
+    double gamma = sh[tid * NW], delta = sh[(NR + tid) * NW];
+#pragma unroll
+    for (int wv = 1; wv < NW; ++wv) {
+      gamma += sh[tid * NW + wv];
+      delta += sh[(NR + tid) * NW + wv];
+    }
+    const double beta = guarded_div(gamma, gammaPrev[tid]);
+    const double alpha = sr_alpha(gamma, delta, beta, alphaPrev[tid]);
+    const bool stop = gamma <= thresh[tid];
+    if (blockIdx.x == 0) {
+      gammaOut[tid] = gamma;
+      done[tid] = stop;
+      if (!stop) {
+        alphaOut[tid] = alpha;
+        betaOut[tid] = beta;
+        iters[tid] += 1;
+      }
+    }
+    shB[tid] = float(beta);
+    shA[tid] = float(alpha);
+    shStop[tid] = stop;
+  }
+  __syncthreads();
+  bool all = true;
+#pragma unroll
+  for (int j = 0; j < NR; ++j) all = all && shStop[j] != 0;
+  if (blockIdx.x == 0 && tid == 0) *allDone = all;
+  if (all) return; // uniform over the grid
+  const int col0 = (4 * tid) & (NR - 1);
+  float b[4], a[4];
+  bool keep[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    b[i] = shB[(col0 + i) & (NR - 1)];
+    a[i] = shA[(col0 + i) & (NR - 1)];
+    keep[i] = shStop[(col0 + i) & (NR - 1)] != 0;
+  }
+  const int64_t total = n * NR, nq = total / 4, stride = int64_t(gridDim.x) * kThreads;
+  for (int64_t k = int64_t(blockIdx.x) * kThreads + tid; k < nq; k += stride) {
+    const float4 wv = load_quad(w, k, true);
+    float4 rv = load_quad(r, k, true), pv = load_quad(p, k, true), sv = load_quad(s, k, true),
+           xv = load_quad(x, k, true);
+    const float4 r0 = rv, p0 = pv, s0 = sv, x0 = xv;
+    pv.x = fmaf(b[0], pv.x, rv.x), pv.y = fmaf(b[1], pv.y, rv.y), pv.z = fmaf(b[2], pv.z, rv.z), pv.w = fmaf(b[3], pv.w, rv.w);
+    sv.x = fmaf(b[0], sv.x, wv.x), sv.y = fmaf(b[1], sv.y, wv.y), sv.z = fmaf(b[2], sv.z, wv.z), sv.w = fmaf(b[3], sv.w, wv.w);
+    xv.x = fmaf(a[0], pv.x, xv.x), xv.y = fmaf(a[1], pv.y, xv.y), xv.z = fmaf(a[2], pv.z, xv.z), xv.w = fmaf(a[3], pv.w, xv.w);
+    rv.x = fmaf(-a[0], sv.x, rv.x), rv.y = fmaf(-a[1], sv.y, rv.y), rv.z = fmaf(-a[2], sv.z, rv.z), rv.w = fmaf(-a[3], sv.w, rv.w);
+    keep_quad(pv, p0, keep);
+    keep_quad(sv, s0, keep);
+    keep_quad(xv, x0, keep);
+    keep_quad(rv, r0, keep);
+    store_quad(p, k, true, pv);
+    store_quad(s, k, true, sv);
+    store_quad(x, k, true, xv);
+    store_quad(r, k, true, rv);
+  }
+  // the total % 4 tail elements (NR = 2 with an odd n only)
+  const int64_t t = nq * 4 + tid;
+  if (blockIdx.x == 0 && t < total && !shStop[t & (NR - 1)]) {
     const float bt = shB[t & (NR - 1)], at = shA[t & (NR - 1)];
     const float rt = r[t];
     const float pt = fmaf(bt, p[t], rt), st = fmaf(bt, s[t], w[t]);
@@ -739,6 +989,155 @@ void cg_sr_update_batch(int64_t n, int k, const double *partialsGamma, const dou
     hipLaunchKernelGGL((cg_sr_update_batch_k<NR>), dim3(dot_partial_count(n * k)), dim3(kThreads), 0, s, n,
                        partialsGamma, partialsDelta, np, gammaPrev, alphaPrev, W, R, P, S, X, gammaOut, alphaOut,
                        betaOut);
+  });
+  TZ_HIP_LAUNCH_CHECK();
+}
+
+// ---- the stopping forms: the argument checks of the kernels they extend, then their own
+
+namespace {
+
+struct Span {
+  const void *p;
+  size_t bytes;
+};
+
+bool overlap(Span a, Span b) {
+  const auto a0 = reinterpret_cast<uintptr_t>(a.p), b0 = reinterpret_cast<uintptr_t>(b.p);
+  return a0 < b0 + b.bytes && b0 < a0 + a.bytes;
+}
+
+// thresh is read by every block while block 0 publishes, and done / iters / all_done are stores
+// of block 0: none may share a byte with a scalar the launch reads or publishes, or with each other
+void check_stop_state(const char *what, int k, const double *gammaPrev, const double *alphaPrev,
+                      const double *gammaOut, const double *alphaOut, const double *betaOut, const double *thresh,
+                      const int *done, const int64_t *iters, const int *allDone) {
+  const std::string w(what);
+  if (!thresh || !done || !iters || (k > 1 && !allDone)) throw std::runtime_error(w + ": null pointer");
+  const size_t n = size_t(k);
+  const Span scal[5] = {{gammaPrev, 8 * n}, {alphaPrev, 8 * n}, {gammaOut, 8 * n}, {alphaOut, 8 * n}, {betaOut, 8 * n}};
+  const Span own[4] = {{thresh, 8 * n}, {done, 4 * n}, {iters, 8 * n}, {allDone, allDone ? 4u : 0u}};
+  for (const Span &o : own)
+    for (const Span &sc : scal)
+      if (o.bytes && overlap(o, sc))
+        throw std::runtime_error(w + ": thresh, done, iters and all_done must not alias the iteration's scalars");
+  for (int i = 0; i < 4; ++i)
+    for (int j = i + 1; j < 4; ++j)
+      if (own[i].bytes && own[j].bytes && overlap(own[i], own[j]))
+        throw std::runtime_error(w + ": thresh, done, iters and all_done must not alias each other");
+}
+
+} // namespace
+
+void csr_spmv_dot2_stop(int nRows, const int32_t *rowPtr, const int32_t *colInd, const float *val, const float *r,
+                        float *w, int lanes, double *partialsGamma, double *partialsDelta, const double *gammaOut,
+                        const double *alphaOut, double *gammaPrev, double *alphaPrev, const int *done,
+                        void *stream) {
+  if (nRows <= 0) throw std::runtime_error("csr_spmv_dot2_stop: nRows must be positive");
+  if (!rowPtr || !colInd || !val || !r || !w || !partialsGamma || !partialsDelta || !done)
+    throw std::runtime_error("csr_spmv_dot2_stop: null pointer");
+  if (partialsGamma == partialsDelta) throw std::runtime_error("csr_spmv_dot2_stop: the two slabs must differ");
+  if (gammaOut || alphaOut || gammaPrev || alphaPrev) {
+    if (!gammaOut || !alphaOut || !gammaPrev || !alphaPrev)
+      throw std::runtime_error("csr_spmv_dot2_stop: null pointer (the four scalars come together or not at all)");
+    // every block reads done while block 0 may already have moved the scalars
+    if (overlap(Span{done, 4}, Span{gammaPrev, 8}) || overlap(Span{done, 4}, Span{alphaPrev, 8}))
+      throw std::runtime_error("csr_spmv_dot2_stop: done must not alias the previous scalars");
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  dispatch_ilp(lanes, "csr_spmv_dot2_stop: lanes must be kSpmvIlp + 1, 2 or 4", [&](auto lanesPerRow, auto k) {
+    constexpr int W = decltype(lanesPerRow)::value, K = decltype(k)::value;
+    const dim3 g(unsigned(spmv_dot_partial_count(nRows, W))), b(kSpmvThreads);
+    hipLaunchKernelGGL((csr_spmv_dot2_stop_k<W, K>), g, b, 0, s, nRows, rowPtr, colInd, val, r, w, partialsGamma,
+                       partialsDelta, gammaOut, alphaOut, gammaPrev, alphaPrev, done);
+  });
+  TZ_HIP_LAUNCH_CHECK();
+}
+
+void cg_sr_update_stop(int64_t n, const double *partialsGamma, const double *partialsDelta, int np,
+                       const double *gammaPrev, const double *alphaPrev, const float *w, float *r, float *p,
+                       float *s, float *x, double *gammaOut, double *alphaOut, double *betaOut,
+                       const double *thresh, int *done, int64_t *iters, void *stream) {
+  check_vec("cg_sr_update_stop", n, w, r);
+  check_vec("cg_sr_update_stop", n, p, s);
+  check_vec("cg_sr_update_stop", n, x, x);
+  check_np("cg_sr_update_stop", partialsGamma, np);
+  check_np("cg_sr_update_stop", partialsDelta, np);
+  if (!gammaPrev || !alphaPrev || !gammaOut || !alphaOut || !betaOut)
+    throw std::runtime_error("cg_sr_update_stop: null pointer");
+  if (gammaOut == gammaPrev || gammaOut == alphaPrev || alphaOut == gammaPrev || alphaOut == alphaPrev ||
+      betaOut == gammaPrev || betaOut == alphaPrev)
+    throw std::runtime_error("cg_sr_update_stop: the published scalars must not alias the previous ones");
+  check_stop_state("cg_sr_update_stop", 1, gammaPrev, alphaPrev, gammaOut, alphaOut, betaOut, thresh, done, iters,
+                   nullptr);
+  hipLaunchKernelGGL(cg_sr_update_stop_k, dim3(dot_partial_count(n)), dim3(kThreads), 0,
+                     static_cast<hipStream_t>(stream), n, partialsGamma, partialsDelta, np, gammaPrev, alphaPrev,
+                     w, r, p, s, x, gammaOut, alphaOut, betaOut, thresh, done, iters);
+  TZ_HIP_LAUNCH_CHECK();
+}
+
+void csr_spmm_dot2_stop(int nRows, const int32_t *rowPtr, const int32_t *colInd, const float *val, const float *R,
+                        float *Wout, int k, int lanes, double *partialsGamma, double *partialsDelta,
+                        const double *gammaOut, const double *alphaOut, double *gammaPrev, double *alphaPrev,
+                        const int *allDone, void *stream) {
+  if (nRows <= 0) throw std::runtime_error("csr_spmm_dot2_stop: nRows must be positive");
+  if (k != 2 && k != 4 && k != 8)
+    throw std::runtime_error("csr_spmm_dot2_stop: k must be 2, 4 or 8 right-hand sides");
+  if (!rowPtr || !colInd || !val || !partialsGamma || !partialsDelta || !allDone)
+    throw std::runtime_error("csr_spmm_dot2_stop: null pointer");
+  check_batch_vec("csr_spmm_dot2_stop", R);
+  check_batch_vec("csr_spmm_dot2_stop", Wout);
+  if (R == Wout) throw std::runtime_error("csr_spmm_dot2_stop: R and Wout must differ");
+  if (overlap(partialsGamma, partialsDelta, k * kCgMaxPartials))
+    throw std::runtime_error("csr_spmm_dot2_stop: the two slab arrays must not overlap");
+  if (gammaOut || alphaOut || gammaPrev || alphaPrev) {
+    if (!gammaOut || !alphaOut || !gammaPrev || !alphaPrev)
+      throw std::runtime_error(
+          "csr_spmm_dot2_stop: null pointer (the four scalar arrays come together or not at all)");
+    if (overlap(Span{allDone, 4}, Span{gammaPrev, 8 * size_t(k)}) ||
+        overlap(Span{allDone, 4}, Span{alphaPrev, 8 * size_t(k)}))
+      throw std::runtime_error("csr_spmm_dot2_stop: all_done must not alias the previous scalars");
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  dispatch_ilp(lanes, "csr_spmm_dot2_stop: lanes must be kSpmvIlp + 1, 2 or 4", [&](auto lanesPerRow, auto depth) {
+    constexpr int W = decltype(lanesPerRow)::value, K = decltype(depth)::value;
+    dispatch_nrhs(k, "csr_spmm_dot2_stop", [&](auto nr) {
+      constexpr int NR = decltype(nr)::value;
+      const dim3 g(unsigned(spmv_dot_partial_count(nRows, W))), b(kSpmvThreads);
+      hipLaunchKernelGGL((csr_spmm_dot2_stop_k<W, K, NR>), g, b, 0, s, nRows, rowPtr, colInd, val, R, Wout,
+                         partialsGamma, partialsDelta, gammaOut, alphaOut, gammaPrev, alphaPrev, allDone);
+    });
+  });
+  TZ_HIP_LAUNCH_CHECK();
+}
+
+void cg_sr_update_batch_stop(int64_t n, int k, const double *partialsGamma, const double *partialsDelta, int np,
+                             const double *gammaPrev, const double *alphaPrev, const float *W, float *R, float *P,
+                             float *S, float *X, double *gammaOut, double *alphaOut, double *betaOut,
+                             const double *thresh, int *done, int64_t *iters, int *allDone, void *stream) {
+  if (n <= 0) throw std::runtime_error("cg_sr_update_batch_stop: n must be positive");
+  if (k != 2 && k != 4 && k != 8)
+    throw std::runtime_error("cg_sr_update_batch_stop: k must be 2, 4 or 8 right-hand sides");
+  for (const void *v : {static_cast<const void *>(W), static_cast<const void *>(R), static_cast<const void *>(P),
+                        static_cast<const void *>(S), static_cast<const void *>(X)})
+    check_batch_vec("cg_sr_update_batch_stop", v);
+  check_np("cg_sr_update_batch_stop", partialsGamma, np);
+  check_np("cg_sr_update_batch_stop", partialsDelta, np);
+  if (!gammaPrev || !alphaPrev || !gammaOut || !alphaOut || !betaOut)
+    throw std::runtime_error("cg_sr_update_batch_stop: null pointer");
+  for (const double *out : {gammaOut, alphaOut, betaOut})
+    if (overlap(out, gammaPrev, k) || overlap(out, alphaPrev, k))
+      throw std::runtime_error("cg_sr_update_batch_stop: the published scalars must not alias the previous ones");
+  if (overlap(gammaOut, alphaOut, k) || overlap(gammaOut, betaOut, k) || overlap(alphaOut, betaOut, k))
+    throw std::runtime_error("cg_sr_update_batch_stop: the three published arrays must not alias each other");
+  check_stop_state("cg_sr_update_batch_stop", k, gammaPrev, alphaPrev, gammaOut, alphaOut, betaOut, thresh, done,
+                   iters, allDone);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  dispatch_nrhs(k, "cg_sr_update_batch_stop", [&](auto nr) {
+    constexpr int NR = decltype(nr)::value;
+    hipLaunchKernelGGL((cg_sr_update_batch_stop_k<NR>), dim3(dot_partial_count(n * k)), dim3(kThreads), 0, s, n,
+                       partialsGamma, partialsDelta, np, gammaPrev, alphaPrev, W, R, P, S, X, gammaOut, alphaOut,
+                       betaOut, thresh, done, iters, allDone);
   });
   TZ_HIP_LAUNCH_CHECK();
 }

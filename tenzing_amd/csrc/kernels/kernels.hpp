@@ -312,6 +312,39 @@ void csr_spmm_dot2(int nRows, const int32_t *rowPtr, const int32_t *colInd, cons
 void cg_sr_update_batch(int64_t n, int k, const double *partials_gamma, const double *partials_delta, int np,
                         const double *gamma_prev, const double *alpha_prev, const float *W, float *R, float *P,
                         float *S, float *X, double *gamma_out, double *alpha_out, double *beta_out, void *stream);
+// ---- the same four launches with a convergence test decided on the device. Every block of the
+// update holds the same bits of gamma = r . r (sum of the gamma slab), so all blocks agree on
+// stop = gamma <= *thresh without any hand-off; a NaN gamma never stops. "Stop" means "freeze":
+// the stopped update writes no vector, the next SpMV returns at once, the update after it sums
+// the same slab and stops again, however often the pair is replayed. thresh, done, iters (and
+// all_done) must not share a byte with the iteration's scalars or with each other.
+/// csr_spmv_dot2, unless *done is set: then every block returns before it writes anything (w,
+/// both slabs and the previous scalars keep what the stopped update read)
+void csr_spmv_dot2_stop(int nRows, const int32_t *rowPtr, const int32_t *colInd, const float *val, const float *r,
+                        float *w, int lanes, double *partials_gamma, double *partials_delta,
+                        const double *gamma_out, const double *alpha_out, double *gamma_prev, double *alpha_prev,
+                        const int *done, void *stream);
+/// cg_sr_update with the test after its prologue. gamma <= *thresh: p, s, x, r, *alpha_out and
+/// *beta_out are not written; block 0 stores *done = 1 and gamma. Otherwise cg_sr_update (same
+/// bits), and block 0 also stores *done = 0 and adds 1 to *iters.
+void cg_sr_update_stop(int64_t n, const double *partials_gamma, const double *partials_delta, int np,
+                       const double *gamma_prev, const double *alpha_prev, const float *w, float *r, float *p,
+                       float *s, float *x, double *gamma_out, double *alpha_out, double *beta_out,
+                       const double *thresh, int *done, int64_t *iters, void *stream);
+/// csr_spmm_dot2, unless *all_done is set (every column has stopped): then nothing is written.
+/// While any column runs, a stopped one is computed again from its unchanged r: the same bits.
+void csr_spmm_dot2_stop(int nRows, const int32_t *rowPtr, const int32_t *colInd, const float *val, const float *R,
+                        float *Wout, int k, int lanes, double *partials_gamma, double *partials_delta,
+                        const double *gamma_out, const double *alpha_out, double *gamma_prev, double *alpha_prev,
+                        const int *all_done, void *stream);
+/// cg_sr_update_batch with one test per column: thresh[k], done[k], iters[k]. Column j with
+/// gamma_j <= thresh[j] keeps its p, s, x, r, alpha_out[j] and beta_out[j] and gets done[j] = 1;
+/// every other column is updated as cg_sr_update_stop updates it alone (same bits), done[j] = 0,
+/// iters[j] += 1. *all_done = the AND of done; once it is 1 no block passes over the vectors.
+void cg_sr_update_batch_stop(int64_t n, int k, const double *partials_gamma, const double *partials_delta, int np,
+                             const double *gamma_prev, const double *alpha_prev, const float *W, float *R, float *P,
+                             float *S, float *X, double *gamma_out, double *alpha_out, double *beta_out,
+                             const double *thresh, int *done, int64_t *iters, int *all_done, void *stream);
 
 /// y += alpha * x (f64)
 void axpy_f64(int64_t n, double alpha, const double *x, double *y, void *stream);

@@ -18,7 +18,9 @@
 //          of the next iteration's spmvdot, which copies them from gamma and alpha (after their
 //          last reader, the update, and before the next one). With nrhs = 2, 4 or 8 the same
 //          two ops run the batched kernels on interleaved vectors: nrhs independent recurrences,
-//          every slab and scalar an array of nrhs with the same writers
+//          every slab and scalar an array of nrhs with the same writers. With tol > 0 the two
+//          ops launch the stopping kernels: thresholds <- the host (reset, set_armed), done,
+//          iters and all_done <- block 0 of the update, read by the next spmvdot (dStop_)
 #include "workloads.hpp"
 
 #include "core/util.hpp"
@@ -45,6 +47,7 @@ Json CgArgs::json() const {
   j["rhs"] = rhs;
   j["nrhs"] = nrhs;
   j["rhs_first"] = rhs_first;
+  j["tol"] = tol;
   j["rank"] = rank;
   j["size"] = size;
   return j;
@@ -111,6 +114,10 @@ ConjugateGradient::ConjugateGradient(CgArgs a) : a_(std::move(a)) {
            "CG with nrhs > 1 needs form sr: only the single-reduction form has batched kernels (got nrhs "
                << a_.nrhs << " with form " << a_.form << ")");
   TZ_CHECK(a_.rhs_first >= 0, "CG rhs_first must not be negative (got " << a_.rhs_first << ")");
+  TZ_CHECK(std::isfinite(a_.tol) && a_.tol >= 0, "CG tol must be finite and not negative (got " << a_.tol << ")");
+  TZ_CHECK(a_.tol == 0 || a_.form == "sr",
+           "CG with tol > 0 needs form sr: only the single-reduction form has kernels that test convergence "
+               << "on the device (got tol " << a_.tol << " with form " << a_.form << ")");
   if (!a_.matrix.empty()) {
     A_ = read_matrix_market(a_.matrix);
     TZ_CHECK(A_.rows == A_.cols, a_.matrix << ": CG needs a square matrix, got " << A_.rows << " x " << A_.cols);
@@ -145,6 +152,13 @@ ConjugateGradient::ConjugateGradient(CgArgs a) : a_(std::move(a)) {
       for (float &v : b_[size_t(c)]) v = float(int64_t(rng() >> 40)) / 8388608.f - 1.f;
     }
   }
+  // the armed thresholds tol^2 * sum_i b[i]^2: the sum in f64 in index order, then one product
+  // with tol * tol
+  for (int c = 0; c < a_.nrhs && a_.tol > 0; ++c) {
+    double bb = 0;
+    for (float v : b_[size_t(c)]) bb += double(v) * double(v);
+    thresh_.push_back(a_.tol * a_.tol * bb);
+  }
   const int W = a_.lanes - kern::kSpmvIlp;
   TZ_CHECK(a_.lanes == -1 || a_.lanes == 0 || W == 1 || W == 2 || W == 4 ||
                (a_.lanes > 0 && a_.lanes <= 64 && (a_.lanes & (a_.lanes - 1)) == 0),
@@ -175,6 +189,7 @@ void ConjugateGradient::setup() {
   dW_ = DeviceBuffer(vb);
   dScal_ = DeviceBuffer((3 * size_t(kern::kCgMaxPartials) + 8) * sizeof(double));
   if (a_.nrhs > 1) dBatch_ = DeviceBuffer((2 * size_t(kern::kCgMaxPartials) + 5) * k * sizeof(double));
+  if (a_.tol > 0) dStop_ = DeviceBuffer(size_t(a_.nrhs) * 20 + 4);
   dX_ = DeviceBuffer(vb);
   reset();
 }
@@ -191,6 +206,11 @@ void ConjugateGradient::reset() {
   TZ_HIP(hipMemset(dScal_.get(), 0, dScal_.bytes()));
   TZ_HIP(hipMemcpy(dR_.get(), dB_.get(), vb, hipMemcpyDeviceToDevice));
   TZ_HIP(hipMemcpy(dP_.get(), dB_.get(), vb, hipMemcpyDeviceToDevice));
+  if (a_.tol > 0) { // iters, done and all_done 0; armed
+    TZ_HIP(hipMemset(dStop_.get(), 0, dStop_.bytes()));
+    armed_ = true;
+    upload_thresholds();
+  }
   if (a_.nrhs > 1) { // the batched form keeps no rr: every scalar array starts at 0
     TZ_HIP(hipMemset(dBatch_.get(), 0, dBatch_.bytes()));
     TZ_HIP(hipDeviceSynchronize());
@@ -199,6 +219,48 @@ void ConjugateGradient::reset() {
   kern::dot_partials_f32(rows(), dR_.as<float>(), dR_.as<float>(), rrp_(), nullptr);
   kern::sum_partials_f64(rrp_(), np_vec(), rr_(), nullptr);
   TZ_HIP(hipDeviceSynchronize());
+}
+
+void ConjugateGradient::upload_thresholds() const {
+  const std::vector<double> off(thresh_.size(), -1.0);
+  TZ_HIP(hipMemcpy(stThresh_(), (armed_ ? thresh_ : off).data(), thresh_.size() * sizeof(double),
+                   hipMemcpyHostToDevice));
+}
+
+void ConjugateGradient::set_armed(bool armed) {
+  TZ_CHECK(ready(), "CG not set up");
+  TZ_CHECK(a_.tol > 0, "CG set_armed: this workload was built with tol = 0 and has no stopping test");
+  TZ_HIP(hipDeviceSynchronize());
+  armed_ = armed;
+  upload_thresholds();
+  if (!armed) TZ_HIP(hipMemset(stDone_(), 0, size_t(a_.nrhs + 1) * sizeof(int))); // done and all_done
+  TZ_HIP(hipDeviceSynchronize());
+}
+
+int64_t ConjugateGradient::iterations(int col) const {
+  TZ_CHECK(ready(), "CG not set up");
+  TZ_CHECK(a_.tol > 0, "CG iterations: this workload was built with tol = 0 and counts nothing");
+  checked(col);
+  TZ_HIP(hipDeviceSynchronize());
+  int64_t v = 0;
+  TZ_HIP(hipMemcpy(&v, stIters_() + col, sizeof v, hipMemcpyDeviceToHost));
+  return v;
+}
+
+bool ConjugateGradient::converged(int col) const {
+  TZ_CHECK(ready(), "CG not set up");
+  TZ_CHECK(a_.tol > 0, "CG converged: this workload was built with tol = 0 and tests nothing");
+  checked(col);
+  TZ_HIP(hipDeviceSynchronize());
+  int v = 0;
+  TZ_HIP(hipMemcpy(&v, stDone_() + col, sizeof v, hipMemcpyDeviceToHost));
+  return v != 0;
+}
+
+double ConjugateGradient::threshold(int col) const {
+  TZ_CHECK(a_.tol > 0, "CG threshold: this workload was built with tol = 0");
+  if (ready()) TZ_HIP(hipDeviceSynchronize());
+  return thresh_[size_t(checked(col))];
 }
 
 int ConjugateGradient::checked(int col) const {
@@ -327,6 +389,17 @@ void ConjugateGradient::fused_p(void *s) const {
 }
 
 void ConjugateGradient::sr_spmv_dot(void *s) const {
+  if (a_.tol > 0) { // the same arguments and, per kernel, the flag the update publishes
+    if (a_.nrhs > 1)
+      kern::csr_spmm_dot2_stop(int(rows()), dRow_.as<int32_t>(), dCol_.as<int32_t>(), dVal_.as<float>(),
+                               dR_.as<float>(), dW_.as<float>(), a_.nrhs, kFusedLanes, bGamma_(), bDelta_(),
+                               bScal_(0), bScal_(1), bScal_(3), bScal_(4), stAllDone_(), s);
+    else
+      kern::csr_spmv_dot2_stop(int(rows()), dRow_.as<int32_t>(), dCol_.as<int32_t>(), dVal_.as<float>(),
+                               dR_.as<float>(), dW_.as<float>(), kFusedLanes, rrp_(), pq_(), srGamma_(),
+                               srAlpha_(), srGammaPrev_(), srAlphaPrev_(), stDone_(), s);
+    return;
+  }
   if (a_.nrhs > 1) {
     kern::csr_spmm_dot2(int(rows()), dRow_.as<int32_t>(), dCol_.as<int32_t>(), dVal_.as<float>(),
                         dR_.as<float>(), dW_.as<float>(), a_.nrhs, kFusedLanes, bGamma_(), bDelta_(), bScal_(0),
@@ -338,6 +411,18 @@ void ConjugateGradient::sr_spmv_dot(void *s) const {
                       srAlphaPrev_(), s);
 }
 void ConjugateGradient::sr_update(void *s) const {
+  if (a_.tol > 0) {
+    if (a_.nrhs > 1)
+      kern::cg_sr_update_batch_stop(rows(), a_.nrhs, bGamma_(), bDelta_(), np_spmv(), bScal_(3), bScal_(4),
+                                    dW_.as<float>(), dR_.as<float>(), dP_.as<float>(), dS_.as<float>(),
+                                    dX_.as<float>(), bScal_(0), bScal_(1), bScal_(2), stThresh_(), stDone_(),
+                                    stIters_(), stAllDone_(), s);
+    else
+      kern::cg_sr_update_stop(rows(), rrp_(), pq_(), np_spmv(), srGammaPrev_(), srAlphaPrev_(), dW_.as<float>(),
+                              dR_.as<float>(), dP_.as<float>(), dS_.as<float>(), dX_.as<float>(), srGamma_(),
+                              srAlpha_(), srBeta_(), stThresh_(), stDone_(), stIters_(), s);
+    return;
+  }
   if (a_.nrhs > 1) {
     kern::cg_sr_update_batch(rows(), a_.nrhs, bGamma_(), bDelta_(), np_spmv(), bScal_(3), bScal_(4),
                              dW_.as<float>(), dR_.as<float>(), dP_.as<float>(), dS_.as<float>(), dX_.as<float>(),

@@ -888,6 +888,11 @@ struct CgArgs {
   // mapping. Column j is solved exactly as a single solve of right-hand side rhs_first + j: same bits.
   int nrhs = 1;
   int rhs_first = 0;
+  // > 0 (form "sr" only): column j stops at r_j . r_j <= tol^2 b_j . b_j, decided on the device
+  // by the stopping kernels (kern::cg_sr_update_stop and its kin), and stays frozen from then on
+  // however many more iterations are launched. 0: the same launches with the same arguments as
+  // before this option existed. The recurrence's r is tested, not the true residual.
+  double tol = 0.0;
   std::string prefix = "cg_";
   int rank = 0, size = 1;
   Json json() const;
@@ -907,8 +912,22 @@ public:
   void add_to_graph(Graph &g);
   /// x = 0, r = p = b, rr = b . b (and the rr partials that sum to it), s = 0 and the
   /// single-reduction form's scalars 0 (its first iteration then has beta = 0); synchronous.
-  /// nrhs > 1: the same per column, b interleaved, every scalar array 0.
+  /// nrhs > 1: the same per column, b interleaved, every scalar array 0. With tol > 0 also
+  /// iterations = 0, not converged, and the stop armed.
   void reset();
+  /// tol > 0 only. false: every threshold becomes -1 and the done flags 0; r . r >= 0 never
+  /// passes, so the stopping kernels run their full path on every launch, which is what a search
+  /// or a timing loop that replays thousands of iterations on one state must measure. true:
+  /// thresholds back to tol^2 b . b. The state after setup() and reset() is armed. Meant to be
+  /// switched on a fresh state (reset() first): a recurrence that has stopped does not resume.
+  void set_armed(bool armed);
+  bool armed() const { return armed_; }
+  /// tol > 0 only, all synchronous: iterations column `col` took before it stopped (or so far),
+  int64_t iterations(int col = 0) const;
+  /// whether its last update found r . r <= threshold,
+  bool converged(int col = 0) const;
+  /// and its armed threshold tol^2 * sum_i b[i]^2 (f64, index order), whatever set_armed says
+  double threshold(int col = 0) const;
   /// column `col` (0 .. nrhs - 1) of the state, de-interleaved; anything else throws
   std::vector<float> x(int col = 0) const { return down(dX_, col); }
   std::vector<float> r(int col = 0) const { return down(dR_, col); }
@@ -975,6 +994,15 @@ private:
   double *bDelta_() const { return dBatch_.as<double>(); }
   double *bGamma_() const { return bDelta_() + a_.nrhs * kern::kCgMaxPartials; }
   double *bScal_(int i) const { return bGamma_() + a_.nrhs * kern::kCgMaxPartials + i * a_.nrhs; }
+  // tol > 0: [thresh: nrhs f64 | iters: nrhs i64 | done: nrhs i32 | all_done: i32]
+  DeviceBuffer dStop_;
+  std::vector<double> thresh_; // the armed thresholds
+  bool armed_ = true;
+  double *stThresh_() const { return dStop_.as<double>(); }
+  int64_t *stIters_() const { return reinterpret_cast<int64_t *>(stThresh_() + a_.nrhs); }
+  int *stDone_() const { return reinterpret_cast<int *>(stIters_() + a_.nrhs); }
+  int *stAllDone_() const { return stDone_() + a_.nrhs; }
+  void upload_thresholds() const;
 };
 
 /// Horizontal fusion (fused_ops.cpp): the halo's self moves `dirs` and the SpMV's local product

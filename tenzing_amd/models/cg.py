@@ -8,7 +8,9 @@ pseudo-random vector. The search chooses between the plain form (8 launches) and
 the single-reduction (Chronopoulos-Gear) recurrence in 2 launches: an SpMV of r that also forms
 r.r and r.(A r), then one update of p, s, x and r; ``form="all"`` offers all three to the search.
 With ``nrhs`` = 2, 4 or 8 the single-reduction form solves that many right-hand sides in the same
-two launches: one matrix stream and one gather per entry serve every column.
+two launches: one matrix stream and one gather per entry serve every column. With ``tol`` > 0
+that form stops each column on the device at r.r <= tol^2 b.b and freezes it; ``solve`` drives a
+prepared runtime until every column has stopped.
 """
 from __future__ import annotations
 
@@ -35,13 +37,17 @@ class CgConfig:
     # right-hand side rhs_first + j; read it with x(j), r(j), p(j), b(j), rr(j), residual(j).
     nrhs: int = 1
     rhs_first: int = 0
+    # > 0 (form="sr" only): column j stops at r_j.r_j <= tol^2 b_j.b_j, decided on the device, and
+    # stays frozen however many more iterations are launched; iterations(j), converged(j) and
+    # threshold(j) report, set_armed(False) switches the test off for timing loops. 0: no test
+    tol: float = 0.0
     prefix: str = "cg_"
 
     def args(self, rank: int = 0, size: int = 1, device: int = -1) -> "_tz.CgArgs":
         a = _tz.CgArgs()
         a.m, a.bw, a.nnz, a.seed = self.m, self.bw, self.nnz, self.seed
         a.matrix, a.form, a.lanes, a.rhs, a.prefix = self.matrix, self.form, self.lanes, self.rhs, self.prefix
-        a.nrhs, a.rhs_first = self.nrhs, self.rhs_first
+        a.nrhs, a.rhs_first, a.tol = self.nrhs, self.rhs_first, self.tol
         a.rank, a.size, a.device = rank, size, device
         return a
 
@@ -56,3 +62,35 @@ def build_cg(cfg: CgConfig, ctrl=None, device: int = -1, setup: bool = True, gra
     g = graph if graph is not None else _tz.Graph()
     c.add_to_graph(g)
     return c, g
+
+
+@dataclasses.dataclass
+class CgSolve:
+    iterations: list   # per column: iterations taken before it stopped (or until max_iters)
+    converged: list    # per column: r.r <= tol^2 b.b was reached
+    launched: int      # iterations launched: at most max(iterations) + check_every, and max_iters
+    residual: list     # per column: the true residual ||b - A x|| / ||b|| of the x it ended with
+    #                    (formed on the host; empty with solve(..., residual=False))
+
+
+def solve(cg, rt, max_iters: int, check_every: int = 8, residual: bool = True) -> CgSolve:
+    """Iterate a ``tol`` > 0 workload from its current state until every column has converged or
+    ``max_iters`` iterations were launched. ``rt`` must have a schedule of this workload's graph
+    prepared. The host looks at the device's flags only every ``check_every`` iterations; the
+    iterations launched past a column's stop leave it untouched, so x, r, p and ``iterations`` do
+    not depend on ``check_every``."""
+    if cg.args.tol <= 0:
+        raise ValueError("solve needs a workload built with tol > 0")
+    if max_iters < 0 or check_every < 1:
+        raise ValueError("solve: max_iters >= 0 and check_every >= 1")
+    cols = range(cg.args.nrhs)
+    launched = 0
+    while launched < max_iters:
+        n = min(check_every, max_iters - launched)
+        rt.run(n)
+        launched += n
+        rt.device_sync()
+        if all(cg.converged(j) for j in cols):
+            break
+    return CgSolve([cg.iterations(j) for j in cols], [cg.converged(j) for j in cols], launched,
+                   [cg.residual(j) for j in cols] if residual else [])
