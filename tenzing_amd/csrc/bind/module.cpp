@@ -143,6 +143,7 @@ py::dict box_to_dict(const kern::BoxDesc &b) {
 }
 
 void *P(uintptr_t p) { return reinterpret_cast<void *>(p); }
+template <typename T> T *as(uintptr_t p) { return reinterpret_cast<T *>(p); }
 
 /// hold a Python object (the tensors behind an op's raw pointers) from C++; released under
 /// the GIL whenever the last C++ owner lets go
@@ -1363,88 +1364,70 @@ PYBIND11_MODULE(_tz, m) {
   k.attr("SPMV_ILP") = kern::kSpmvIlp;
   k.def("dot_partial_count", &kern::dot_partial_count, py::arg("n"));
   k.def("spmv_dot_partial_count", &kern::spmv_dot_partial_count, py::arg("n_rows"), py::arg("lanes"));
+  using cf = const float;
+  using cd = const double;
+  using ci32 = const int32_t;
   k.def("dot_partials_f32", [](int64_t n, uintptr_t u, uintptr_t v, uintptr_t part, uintptr_t s) {
-    kern::dot_partials_f32(n, reinterpret_cast<const float *>(u), reinterpret_cast<const float *>(v),
-                           reinterpret_cast<double *>(part), P(s));
+    kern::dot_partials_f32(n, as<cf>(u), as<cf>(v), as<double>(part), P(s));
   }, py::arg("n"), py::arg("u"), py::arg("v"), py::arg("partials"), py::arg("stream") = 0);
   k.def("sum_partials_f64", [](uintptr_t part, int np, uintptr_t out, uintptr_t s) {
-    kern::sum_partials_f64(reinterpret_cast<const double *>(part), np, reinterpret_cast<double *>(out), P(s));
+    kern::sum_partials_f64(as<cd>(part), np, as<double>(out), P(s));
   }, py::arg("partials"), py::arg("np"), py::arg("out"), py::arg("stream") = 0);
   k.def("cg_alpha", [](uintptr_t part, int np, uintptr_t rr, uintptr_t alpha, uintptr_t s) {
-    kern::cg_alpha(reinterpret_cast<const double *>(part), np, reinterpret_cast<const double *>(rr),
-                   reinterpret_cast<double *>(alpha), P(s));
+    kern::cg_alpha(as<cd>(part), np, as<cd>(rr), as<double>(alpha), P(s));
   }, py::arg("partials_pq"), py::arg("np"), py::arg("rr"), py::arg("alpha"), py::arg("stream") = 0);
   k.def("cg_beta", [](uintptr_t part, int np, uintptr_t rr, uintptr_t beta, uintptr_t s) {
-    kern::cg_beta(reinterpret_cast<const double *>(part), np, reinterpret_cast<double *>(rr),
-                  reinterpret_cast<double *>(beta), P(s));
+    kern::cg_beta(as<cd>(part), np, as<double>(rr), as<double>(beta), P(s));
   }, py::arg("partials_rr"), py::arg("np"), py::arg("rr"), py::arg("beta"), py::arg("stream") = 0);
   k.def("axpy_dev_f32", [](int64_t n, uintptr_t sc, int sign, uintptr_t x, uintptr_t y, uintptr_t s) {
-    kern::axpy_dev_f32(n, reinterpret_cast<const double *>(sc), sign, reinterpret_cast<const float *>(x),
-                       reinterpret_cast<float *>(y), P(s));
+    kern::axpy_dev_f32(n, as<cd>(sc), sign, as<cf>(x), as<float>(y), P(s));
   }, py::arg("n"), py::arg("scalar"), py::arg("sign"), py::arg("x"), py::arg("y"), py::arg("stream") = 0);
   k.def("xpay_dev_f32", [](int64_t n, uintptr_t sc, uintptr_t x, uintptr_t y, uintptr_t s) {
-    kern::xpay_dev_f32(n, reinterpret_cast<const double *>(sc), reinterpret_cast<const float *>(x),
-                       reinterpret_cast<float *>(y), P(s));
+    kern::xpay_dev_f32(n, as<cd>(sc), as<cf>(x), as<float>(y), P(s));
   }, py::arg("n"), py::arg("scalar"), py::arg("x"), py::arg("y"), py::arg("stream") = 0);
   k.def("csr_spmv_dot", [](int n, uintptr_t rp, uintptr_t ci, uintptr_t v, uintptr_t p, uintptr_t q, int lanes,
                            uintptr_t pq, uintptr_t prr, int npRr, uintptr_t rr, uintptr_t s) {
-    kern::csr_spmv_dot(n, reinterpret_cast<const int32_t *>(rp), reinterpret_cast<const int32_t *>(ci),
-                       reinterpret_cast<const float *>(v), reinterpret_cast<const float *>(p),
-                       reinterpret_cast<float *>(q), lanes, reinterpret_cast<double *>(pq),
-                       reinterpret_cast<const double *>(prr), npRr, reinterpret_cast<double *>(rr), P(s));
+    kern::csr_spmv_dot(n, as<ci32>(rp), as<ci32>(ci), as<cf>(v), as<cf>(p), as<float>(q), lanes, as<double>(pq),
+                       as<cd>(prr), npRr, as<double>(rr), P(s));
   }, py::arg("n_rows"), py::arg("row_ptr"), py::arg("col_ind"), py::arg("val"), py::arg("p"), py::arg("q"),
      py::arg("lanes"), py::arg("partials_pq"), py::arg("partials_rr") = 0, py::arg("np_rr") = 0,
      py::arg("rr") = 0, py::arg("stream") = 0);
   k.def("cg_fused_x", [](int64_t n, uintptr_t pq, int np, uintptr_t rr, uintptr_t p, uintptr_t x, uintptr_t s) {
-    kern::cg_fused_x(n, reinterpret_cast<const double *>(pq), np, reinterpret_cast<const double *>(rr),
-                     reinterpret_cast<const float *>(p), reinterpret_cast<float *>(x), P(s));
+    kern::cg_fused_x(n, as<cd>(pq), np, as<cd>(rr), as<cf>(p), as<float>(x), P(s));
   }, py::arg("n"), py::arg("partials_pq"), py::arg("np"), py::arg("rr"), py::arg("p"), py::arg("x"),
      py::arg("stream") = 0);
   k.def("cg_fused_r", [](int64_t n, uintptr_t pq, int np, uintptr_t rr, uintptr_t q, uintptr_t r, uintptr_t prr,
                          uintptr_t s) {
-    kern::cg_fused_r(n, reinterpret_cast<const double *>(pq), np, reinterpret_cast<const double *>(rr),
-                     reinterpret_cast<const float *>(q), reinterpret_cast<float *>(r),
-                     reinterpret_cast<double *>(prr), P(s));
+    kern::cg_fused_r(n, as<cd>(pq), np, as<cd>(rr), as<cf>(q), as<float>(r), as<double>(prr), P(s));
   }, py::arg("n"), py::arg("partials_pq"), py::arg("np"), py::arg("rr"), py::arg("q"), py::arg("r"),
      py::arg("partials_rr"), py::arg("stream") = 0);
   k.def("cg_fused_p", [](int64_t n, uintptr_t prr, int np, uintptr_t rr, uintptr_t r, uintptr_t p, uintptr_t s) {
-    kern::cg_fused_p(n, reinterpret_cast<const double *>(prr), np, reinterpret_cast<const double *>(rr),
-                     reinterpret_cast<const float *>(r), reinterpret_cast<float *>(p), P(s));
+    kern::cg_fused_p(n, as<cd>(prr), np, as<cd>(rr), as<cf>(r), as<float>(p), P(s));
   }, py::arg("n"), py::arg("partials_rr"), py::arg("np"), py::arg("rr"), py::arg("r"), py::arg("p"),
      py::arg("stream") = 0);
   k.def("csr_spmv_dot2", [](int n, uintptr_t rp, uintptr_t ci, uintptr_t v, uintptr_t r, uintptr_t w, int lanes,
                             uintptr_t pg, uintptr_t pd, uintptr_t gOut, uintptr_t aOut, uintptr_t gPrev,
                             uintptr_t aPrev, uintptr_t s) {
-    kern::csr_spmv_dot2(n, reinterpret_cast<const int32_t *>(rp), reinterpret_cast<const int32_t *>(ci),
-                        reinterpret_cast<const float *>(v), reinterpret_cast<const float *>(r),
-                        reinterpret_cast<float *>(w), lanes, reinterpret_cast<double *>(pg),
-                        reinterpret_cast<double *>(pd), reinterpret_cast<const double *>(gOut),
-                        reinterpret_cast<const double *>(aOut), reinterpret_cast<double *>(gPrev),
-                        reinterpret_cast<double *>(aPrev), P(s));
+    kern::csr_spmv_dot2(n, as<ci32>(rp), as<ci32>(ci), as<cf>(v), as<cf>(r), as<float>(w), lanes, as<double>(pg),
+                        as<double>(pd), as<cd>(gOut), as<cd>(aOut), as<double>(gPrev), as<double>(aPrev), P(s));
   }, py::arg("n_rows"), py::arg("row_ptr"), py::arg("col_ind"), py::arg("val"), py::arg("r"), py::arg("w"),
      py::arg("lanes"), py::arg("partials_gamma"), py::arg("partials_delta"), py::arg("gamma_out") = 0,
      py::arg("alpha_out") = 0, py::arg("gamma_prev") = 0, py::arg("alpha_prev") = 0, py::arg("stream") = 0);
   k.def("cg_sr_update", [](int64_t n, uintptr_t pg, uintptr_t pd, int np, uintptr_t gPrev, uintptr_t aPrev,
                            uintptr_t w, uintptr_t r, uintptr_t p, uintptr_t sv, uintptr_t x, uintptr_t gOut,
                            uintptr_t aOut, uintptr_t bOut, uintptr_t s) {
-    kern::cg_sr_update(n, reinterpret_cast<const double *>(pg), reinterpret_cast<const double *>(pd), np,
-                       reinterpret_cast<const double *>(gPrev), reinterpret_cast<const double *>(aPrev),
-                       reinterpret_cast<const float *>(w), reinterpret_cast<float *>(r),
-                       reinterpret_cast<float *>(p), reinterpret_cast<float *>(sv), reinterpret_cast<float *>(x),
-                       reinterpret_cast<double *>(gOut), reinterpret_cast<double *>(aOut),
-                       reinterpret_cast<double *>(bOut), P(s));
+    kern::cg_sr_update(n, as<cd>(pg), as<cd>(pd), np, as<cd>(gPrev), as<cd>(aPrev), as<cf>(w), as<float>(r),
+                       as<float>(p), as<float>(sv), as<float>(x), as<double>(gOut), as<double>(aOut),
+                       as<double>(bOut), P(s));
   }, py::arg("n"), py::arg("partials_gamma"), py::arg("partials_delta"), py::arg("np"), py::arg("gamma_prev"),
      py::arg("alpha_prev"), py::arg("w"), py::arg("r"), py::arg("p"), py::arg("s"), py::arg("x"),
      py::arg("gamma_out"), py::arg("alpha_out"), py::arg("beta_out"), py::arg("stream") = 0);
   k.def("csr_spmm_dot2", [](int n, uintptr_t rp, uintptr_t ci, uintptr_t v, uintptr_t r, uintptr_t w, int nrhs,
                             int lanes, uintptr_t pg, uintptr_t pd, uintptr_t gOut, uintptr_t aOut,
                             uintptr_t gPrev, uintptr_t aPrev, uintptr_t s) {
-    kern::csr_spmm_dot2(n, reinterpret_cast<const int32_t *>(rp), reinterpret_cast<const int32_t *>(ci),
-                        reinterpret_cast<const float *>(v), reinterpret_cast<const float *>(r),
-                        reinterpret_cast<float *>(w), nrhs, lanes, reinterpret_cast<double *>(pg),
-                        reinterpret_cast<double *>(pd), reinterpret_cast<const double *>(gOut),
-                        reinterpret_cast<const double *>(aOut), reinterpret_cast<double *>(gPrev),
-                        reinterpret_cast<double *>(aPrev), P(s));
+    kern::csr_spmm_dot2(n, as<ci32>(rp), as<ci32>(ci), as<cf>(v), as<cf>(r), as<float>(w), nrhs, lanes,
+                        as<double>(pg), as<double>(pd), as<cd>(gOut), as<cd>(aOut), as<double>(gPrev),
+                        as<double>(aPrev), P(s));
   }, py::arg("n_rows"), py::arg("row_ptr"), py::arg("col_ind"), py::arg("val"), py::arg("r"), py::arg("w"),
      py::arg("k"), py::arg("lanes"), py::arg("partials_gamma"), py::arg("partials_delta"),
      py::arg("gamma_out") = 0, py::arg("alpha_out") = 0, py::arg("gamma_prev") = 0, py::arg("alpha_prev") = 0,
@@ -1452,24 +1435,18 @@ PYBIND11_MODULE(_tz, m) {
   k.def("cg_sr_update_batch", [](int64_t n, int nrhs, uintptr_t pg, uintptr_t pd, int np, uintptr_t gPrev,
                                  uintptr_t aPrev, uintptr_t w, uintptr_t r, uintptr_t p, uintptr_t sv, uintptr_t x,
                                  uintptr_t gOut, uintptr_t aOut, uintptr_t bOut, uintptr_t s) {
-    kern::cg_sr_update_batch(n, nrhs, reinterpret_cast<const double *>(pg), reinterpret_cast<const double *>(pd),
-                             np, reinterpret_cast<const double *>(gPrev), reinterpret_cast<const double *>(aPrev),
-                             reinterpret_cast<const float *>(w), reinterpret_cast<float *>(r),
-                             reinterpret_cast<float *>(p), reinterpret_cast<float *>(sv),
-                             reinterpret_cast<float *>(x), reinterpret_cast<double *>(gOut),
-                             reinterpret_cast<double *>(aOut), reinterpret_cast<double *>(bOut), P(s));
+    kern::cg_sr_update_batch(n, nrhs, as<cd>(pg), as<cd>(pd), np, as<cd>(gPrev), as<cd>(aPrev), as<cf>(w),
+                             as<float>(r), as<float>(p), as<float>(sv), as<float>(x), as<double>(gOut),
+                             as<double>(aOut), as<double>(bOut), P(s));
   }, py::arg("n"), py::arg("k"), py::arg("partials_gamma"), py::arg("partials_delta"), py::arg("np"),
      py::arg("gamma_prev"), py::arg("alpha_prev"), py::arg("w"), py::arg("r"), py::arg("p"), py::arg("s"),
      py::arg("x"), py::arg("gamma_out"), py::arg("alpha_out"), py::arg("beta_out"), py::arg("stream") = 0);
   k.def("csr_spmv_dot2_stop", [](int n, uintptr_t rp, uintptr_t ci, uintptr_t v, uintptr_t r, uintptr_t w,
                                  int lanes, uintptr_t pg, uintptr_t pd, uintptr_t gOut, uintptr_t aOut,
                                  uintptr_t gPrev, uintptr_t aPrev, uintptr_t done, uintptr_t s) {
-    kern::csr_spmv_dot2_stop(n, reinterpret_cast<const int32_t *>(rp), reinterpret_cast<const int32_t *>(ci),
-                             reinterpret_cast<const float *>(v), reinterpret_cast<const float *>(r),
-                             reinterpret_cast<float *>(w), lanes, reinterpret_cast<double *>(pg),
-                             reinterpret_cast<double *>(pd), reinterpret_cast<const double *>(gOut),
-                             reinterpret_cast<const double *>(aOut), reinterpret_cast<double *>(gPrev),
-                             reinterpret_cast<double *>(aPrev), reinterpret_cast<const int *>(done), P(s));
+    kern::csr_spmv_dot2_stop(n, as<ci32>(rp), as<ci32>(ci), as<cf>(v), as<cf>(r), as<float>(w), lanes,
+                             as<double>(pg), as<double>(pd), as<cd>(gOut), as<cd>(aOut), as<double>(gPrev),
+                             as<double>(aPrev), as<const int>(done), P(s));
   }, py::arg("n_rows"), py::arg("row_ptr"), py::arg("col_ind"), py::arg("val"), py::arg("r"), py::arg("w"),
      py::arg("lanes"), py::arg("partials_gamma"), py::arg("partials_delta"), py::arg("gamma_out"),
      py::arg("alpha_out"), py::arg("gamma_prev"), py::arg("alpha_prev"), py::arg("done"), py::arg("stream") = 0);
@@ -1477,14 +1454,9 @@ PYBIND11_MODULE(_tz, m) {
                                 uintptr_t w, uintptr_t r, uintptr_t p, uintptr_t sv, uintptr_t x, uintptr_t gOut,
                                 uintptr_t aOut, uintptr_t bOut, uintptr_t thresh, uintptr_t done, uintptr_t iters,
                                 uintptr_t s) {
-    kern::cg_sr_update_stop(n, reinterpret_cast<const double *>(pg), reinterpret_cast<const double *>(pd), np,
-                            reinterpret_cast<const double *>(gPrev), reinterpret_cast<const double *>(aPrev),
-                            reinterpret_cast<const float *>(w), reinterpret_cast<float *>(r),
-                            reinterpret_cast<float *>(p), reinterpret_cast<float *>(sv),
-                            reinterpret_cast<float *>(x), reinterpret_cast<double *>(gOut),
-                            reinterpret_cast<double *>(aOut), reinterpret_cast<double *>(bOut),
-                            reinterpret_cast<const double *>(thresh), reinterpret_cast<int *>(done),
-                            reinterpret_cast<int64_t *>(iters), P(s));
+    kern::cg_sr_update_stop(n, as<cd>(pg), as<cd>(pd), np, as<cd>(gPrev), as<cd>(aPrev), as<cf>(w), as<float>(r),
+                            as<float>(p), as<float>(sv), as<float>(x), as<double>(gOut), as<double>(aOut),
+                            as<double>(bOut), as<cd>(thresh), as<int>(done), as<int64_t>(iters), P(s));
   }, py::arg("n"), py::arg("partials_gamma"), py::arg("partials_delta"), py::arg("np"), py::arg("gamma_prev"),
      py::arg("alpha_prev"), py::arg("w"), py::arg("r"), py::arg("p"), py::arg("s"), py::arg("x"),
      py::arg("gamma_out"), py::arg("alpha_out"), py::arg("beta_out"), py::arg("thresh"), py::arg("done"),
@@ -1492,12 +1464,9 @@ PYBIND11_MODULE(_tz, m) {
   k.def("csr_spmm_dot2_stop", [](int n, uintptr_t rp, uintptr_t ci, uintptr_t v, uintptr_t r, uintptr_t w,
                                  int nrhs, int lanes, uintptr_t pg, uintptr_t pd, uintptr_t gOut, uintptr_t aOut,
                                  uintptr_t gPrev, uintptr_t aPrev, uintptr_t allDone, uintptr_t s) {
-    kern::csr_spmm_dot2_stop(n, reinterpret_cast<const int32_t *>(rp), reinterpret_cast<const int32_t *>(ci),
-                             reinterpret_cast<const float *>(v), reinterpret_cast<const float *>(r),
-                             reinterpret_cast<float *>(w), nrhs, lanes, reinterpret_cast<double *>(pg),
-                             reinterpret_cast<double *>(pd), reinterpret_cast<const double *>(gOut),
-                             reinterpret_cast<const double *>(aOut), reinterpret_cast<double *>(gPrev),
-                             reinterpret_cast<double *>(aPrev), reinterpret_cast<const int *>(allDone), P(s));
+    kern::csr_spmm_dot2_stop(n, as<ci32>(rp), as<ci32>(ci), as<cf>(v), as<cf>(r), as<float>(w), nrhs, lanes,
+                             as<double>(pg), as<double>(pd), as<cd>(gOut), as<cd>(aOut), as<double>(gPrev),
+                             as<double>(aPrev), as<const int>(allDone), P(s));
   }, py::arg("n_rows"), py::arg("row_ptr"), py::arg("col_ind"), py::arg("val"), py::arg("r"), py::arg("w"),
      py::arg("k"), py::arg("lanes"), py::arg("partials_gamma"), py::arg("partials_delta"), py::arg("gamma_out"),
      py::arg("alpha_out"), py::arg("gamma_prev"), py::arg("alpha_prev"), py::arg("all_done"),
@@ -1507,15 +1476,10 @@ PYBIND11_MODULE(_tz, m) {
                                       uintptr_t x, uintptr_t gOut, uintptr_t aOut, uintptr_t bOut,
                                       uintptr_t thresh, uintptr_t done, uintptr_t iters, uintptr_t allDone,
                                       uintptr_t s) {
-    kern::cg_sr_update_batch_stop(n, nrhs, reinterpret_cast<const double *>(pg),
-                                  reinterpret_cast<const double *>(pd), np,
-                                  reinterpret_cast<const double *>(gPrev), reinterpret_cast<const double *>(aPrev),
-                                  reinterpret_cast<const float *>(w), reinterpret_cast<float *>(r),
-                                  reinterpret_cast<float *>(p), reinterpret_cast<float *>(sv),
-                                  reinterpret_cast<float *>(x), reinterpret_cast<double *>(gOut),
-                                  reinterpret_cast<double *>(aOut), reinterpret_cast<double *>(bOut),
-                                  reinterpret_cast<const double *>(thresh), reinterpret_cast<int *>(done),
-                                  reinterpret_cast<int64_t *>(iters), reinterpret_cast<int *>(allDone), P(s));
+    kern::cg_sr_update_batch_stop(n, nrhs, as<cd>(pg), as<cd>(pd), np, as<cd>(gPrev), as<cd>(aPrev), as<cf>(w),
+                                  as<float>(r), as<float>(p), as<float>(sv), as<float>(x), as<double>(gOut),
+                                  as<double>(aOut), as<double>(bOut), as<cd>(thresh), as<int>(done),
+                                  as<int64_t>(iters), as<int>(allDone), P(s));
   }, py::arg("n"), py::arg("k"), py::arg("partials_gamma"), py::arg("partials_delta"), py::arg("np"),
      py::arg("gamma_prev"), py::arg("alpha_prev"), py::arg("w"), py::arg("r"), py::arg("p"), py::arg("s"),
      py::arg("x"), py::arg("gamma_out"), py::arg("alpha_out"), py::arg("beta_out"), py::arg("thresh"),

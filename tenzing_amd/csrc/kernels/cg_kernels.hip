@@ -1,8 +1,9 @@
 // Conjugate-gradient kernels for gfx950: dot products, vector updates whose coefficient lives in
 // device memory, the fused forms (SpMV + dot, update + dot) and the single-reduction form's two
 // kernels (SpMV + two dots, one update of p, s, x and r), those two also for 2, 4 or 8 interleaved
-// right-hand sides, and all four again with a convergence test decided on the device (*_stop).
-// Not in the reference.
+// right-hand sides, and all four again with a convergence test decided on the device (*_stop):
+// eight entry points over four bodies, a stopping one being its test in front of its parent's
+// body. Not in the reference.
 //
 // Vectors are f32; dot products accumulate in f64 (the product of two f32 values is exact in
 // f64); every scalar (rr, alpha, beta) is an f64 in device memory, so no launch argument carries
@@ -27,6 +28,7 @@
 #include "spmv_device.hpp"
 
 #include <algorithm>
+#include <initializer_list>
 #include <stdexcept>
 #include <string>
 
@@ -245,25 +247,33 @@ __global__ __launch_bounds__(kSpmvThreads) void csr_spmv_dot_k(int nRows, const 
   if (threadIdx.x == 0) partialsPq[blockIdx.x] = s;
 }
 
-// The single-reduction (Chronopoulos-Gear) recurrence: both dot products of an iteration come
-// from the same vectors, gamma = r . r and delta = r . (A r), so both ride on the SpMV.
+// ---- The single-reduction (Chronopoulos-Gear) recurrence: both dot products of an iteration
+// come from the same vectors, gamma = r . r and delta = r . (A r), so both ride on the SpMV. Two
+// launches per iteration, each for one right-hand side or for NR interleaved ones, and each of
+// those four with or without a convergence test: eight entry points over four bodies. An entry
+// point with the test (*_stop_k) is its test followed by the body its parent calls, so the two
+// agree bit for bit by construction, not by copying.
 //
+// The test needs no hand-off inside a launch (rule 2). Every block of the update sums the same
+// gamma slab in the same order, so gamma = r . r has the same bits in every block and `gamma <=
+// *thresh` (thresh in device memory) sends the whole grid the same way: a stopped update writes no
+// vector. Block 0 records the outcome in *done and the next launch reads it, as gammaOut and
+// alphaOut travel. A set flag returns every block of the SpMV before it writes, so w, both slabs
+// and the previous scalars keep what the stopped update saw; the next update forms the same gamma
+// and stops again: a stopped iteration stays stopped under any number of replays. A NaN gamma
+// compares false and never stops. tests/test_gpu_cg_tol_kernels.py holds each stopping kernel to
+// its parent's bits all the same.
+
 // w = A r as csr_spmv_dot_k computes q (same row body, same grid) and the block's partials of
 // gamma and delta. Block 0 also moves the scalars the previous update published into the places
 // the next update reads (gammaOut may be null): this launch lies between their writer and their
 // next reader, and nothing in it reads either side.
 template <int W, int K>
-__global__ __launch_bounds__(kSpmvThreads) void csr_spmv_dot2_k(int nRows, const int32_t *__restrict__ rowPtr,
-                                                                const int32_t *__restrict__ colInd,
-                                                                const float *__restrict__ val,
-                                                                const float *__restrict__ r,
-                                                                float *__restrict__ w,
-                                                                double *__restrict__ partialsGamma,
-                                                                double *__restrict__ partialsDelta,
-                                                                const double *__restrict__ gammaOut,
-                                                                const double *__restrict__ alphaOut,
-                                                                double *__restrict__ gammaPrev,
-                                                                double *__restrict__ alphaPrev) {
+__device__ __forceinline__ void spmv_dot2_body(
+    int nRows, const int32_t *__restrict__ rowPtr, const int32_t *__restrict__ colInd,
+    const float *__restrict__ val, const float *__restrict__ r, float *__restrict__ w,
+    double *__restrict__ partialsGamma, double *__restrict__ partialsDelta, const double *__restrict__ gammaOut,
+    const double *__restrict__ alphaOut, double *__restrict__ gammaPrev, double *__restrict__ alphaPrev) {
   __shared__ double sh[kSpmvThreads / 64];
   if (gammaOut && blockIdx.x == 0 && threadIdx.x == 0) {
     *gammaPrev = *gammaOut;
@@ -290,16 +300,16 @@ __global__ __launch_bounds__(kSpmvThreads) void csr_spmv_dot2_k(int nRows, const
   }
 }
 
-// The stopping forms (the four kernels named *_stop_k) add a convergence test that needs no
-// hand-off inside a launch (rule 2). Every block of the update sums the same gamma slab in the
-// same order, so gamma = r . r has the same bits in every block and `gamma <= *thresh` (thresh in
-// device memory) sends the whole grid the same way: a stopped update writes no vector. Block 0
-// records the outcome in *done and the next launch reads it, as gammaOut and alphaOut travel. A
-// set flag returns every block of the SpMV before it writes, so w, both slabs and the previous
-// scalars keep what the stopped update saw; the next update forms the same gamma and stops again:
-// a stopped iteration stays stopped under any number of replays. A NaN gamma compares false and
-// never stops. Each stopping kernel repeats its parent line for line after the test (the parents
-// stay as they were compiled), and tests/test_gpu_cg_tol_kernels.py holds the two to the same bits.
+template <int W, int K>
+__global__ __launch_bounds__(kSpmvThreads) void csr_spmv_dot2_k(
+    int nRows, const int32_t *__restrict__ rowPtr, const int32_t *__restrict__ colInd,
+    const float *__restrict__ val, const float *__restrict__ r, float *__restrict__ w,
+    double *__restrict__ partialsGamma, double *__restrict__ partialsDelta, const double *__restrict__ gammaOut,
+    const double *__restrict__ alphaOut, double *__restrict__ gammaPrev, double *__restrict__ alphaPrev) {
+  spmv_dot2_body<W, K>(nRows, rowPtr, colInd, val, r, w, partialsGamma, partialsDelta, gammaOut, alphaOut,
+                       gammaPrev, alphaPrev);
+}
+
 template <int W, int K>
 __global__ __launch_bounds__(kSpmvThreads) void csr_spmv_dot2_stop_k(
     int nRows, const int32_t *__restrict__ rowPtr, const int32_t *__restrict__ colInd,
@@ -307,37 +317,15 @@ __global__ __launch_bounds__(kSpmvThreads) void csr_spmv_dot2_stop_k(
     double *__restrict__ partialsGamma, double *__restrict__ partialsDelta, const double *__restrict__ gammaOut,
     const double *__restrict__ alphaOut, double *__restrict__ gammaPrev, double *__restrict__ alphaPrev,
     const int *__restrict__ done) {
-  __shared__ double sh[kSpmvThreads / 64];
   if (*done) return; // uniform over the grid
-  if (gammaOut && blockIdx.x == 0 && threadIdx.x == 0) {
-    *gammaPrev = *gammaOut;
-    *alphaPrev = *alphaOut;
-  }
-  const int lane = threadIdx.x & (W - 1);
-  const int rowsPerPass = int(gridDim.x) * (kSpmvThreads / W);
-  double accG = 0.0, accD = 0.0;
-  // whole W-lane groups leave the loop together (W divides 64)
-  for (int row = (blockIdx.x * kSpmvThreads + threadIdx.x) / W; row < nRows; row += rowsPerPass) {
-    const float sum = dev::csr_spmv_ilp_sum<W, K>(row, lane, rowPtr, colInd, val, r);
-    if (lane == 0) {
-      const double ri = double(r[row]);
-      w[row] = sum;
-      accG += ri * ri;
-      accD += ri * double(sum);
-    }
-  }
-  const double g = block_sum<kSpmvThreads / 64>(accG, sh);
-  const double d = block_sum<kSpmvThreads / 64>(accD, sh);
-  if (threadIdx.x == 0) {
-    partialsGamma[blockIdx.x] = g;
-    partialsDelta[blockIdx.x] = d;
-  }
+  spmv_dot2_body<W, K>(nRows, rowPtr, colInd, val, r, w, partialsGamma, partialsDelta, gammaOut, alphaOut,
+                       gammaPrev, alphaPrev);
 }
 
-// N block_sums behind one barrier, for a block whose result only leaves through one store per
-// value: the same butterfly per value, then thread i < N adds the NW wave sums of value i in wave
-// order and returns block_sum<NW>(v[i])'s bits (other threads: unspecified). sh: N * NW doubles.
-template <int NW, int N> __device__ __forceinline__ double block_sum_n(double (&v)[N], double *sh) {
+// N block_sums behind one barrier, in two steps. wave_sums: the same butterfly per value, then
+// the NW wave sums of value i in sh[i * NW ..] (N * NW doubles) and the barrier. wave_total: the
+// wave sums of value i added in wave order, block_sum<NW>(v[i])'s bits in whichever thread asks.
+template <int NW, int N> __device__ __forceinline__ void wave_sums(double (&v)[N], double *sh) {
 #pragma unroll
   for (int i = 0; i < N; ++i) {
 #pragma unroll
@@ -348,31 +336,34 @@ template <int NW, int N> __device__ __forceinline__ double block_sum_n(double (&
     for (int i = 0; i < N; ++i) sh[i * NW + (threadIdx.x >> 6)] = v[i];
   }
   __syncthreads();
-  const int i = int(threadIdx.x) < N ? int(threadIdx.x) : 0;
+}
+
+template <int NW> __device__ __forceinline__ double wave_total(const double *sh, int i) {
   double s = sh[i * NW];
 #pragma unroll
   for (int w = 1; w < NW; ++w) s += sh[i * NW + w];
   return s;
 }
 
-// csr_spmv_dot2_k for NR right-hand sides, interleaved (element (i, j) of R and Wout at i * NR +
+// For a block whose result only leaves through one store per value: thread i < N returns the
+// sum of value i (other threads: unspecified)
+template <int NW, int N> __device__ __forceinline__ double block_sum_n(double (&v)[N], double *sh) {
+  wave_sums<NW>(v, sh);
+  return wave_total<NW>(sh, int(threadIdx.x) < N ? int(threadIdx.x) : 0);
+}
+
+// spmv_dot2_body for NR right-hand sides, interleaved (element (i, j) of R and Wout at i * NR +
 // j): the same grid and the same row -> lane group -> block mapping, and per column the same
 // entry order, fmaf chain, xor reduction and block_sum (dev::csr_spmm_ilp_sum, block_sum_n). So
 // column j of Wout and slab j of both partial arrays (slab j starts at j * kCgMaxPartials) have
 // the bits csr_spmv_dot2_k writes for column j alone, while the matrix is streamed once and an
 // entry's NR x values come from one line. Block 0 moves the NR published gammas and alphas.
 template <int W, int K, int NR>
-__global__ __launch_bounds__(kSpmvThreads) void csr_spmm_dot2_k(int nRows, const int32_t *__restrict__ rowPtr,
-                                                                const int32_t *__restrict__ colInd,
-                                                                const float *__restrict__ val,
-                                                                const float *__restrict__ r,
-                                                                float *__restrict__ w,
-                                                                double *__restrict__ partialsGamma,
-                                                                double *__restrict__ partialsDelta,
-                                                                const double *__restrict__ gammaOut,
-                                                                const double *__restrict__ alphaOut,
-                                                                double *__restrict__ gammaPrev,
-                                                                double *__restrict__ alphaPrev) {
+__device__ __forceinline__ void spmm_dot2_body(
+    int nRows, const int32_t *__restrict__ rowPtr, const int32_t *__restrict__ colInd,
+    const float *__restrict__ val, const float *__restrict__ r, float *__restrict__ w,
+    double *__restrict__ partialsGamma, double *__restrict__ partialsDelta, const double *__restrict__ gammaOut,
+    const double *__restrict__ alphaOut, double *__restrict__ gammaPrev, double *__restrict__ alphaPrev) {
   __shared__ double sh[2 * NR * (kSpmvThreads / 64)];
   if (gammaOut && blockIdx.x == 0 && int(threadIdx.x) < NR) {
     gammaPrev[threadIdx.x] = gammaOut[threadIdx.x];
@@ -404,9 +395,19 @@ __global__ __launch_bounds__(kSpmvThreads) void csr_spmm_dot2_k(int nRows, const
   else if (t < 2 * NR) partialsDelta[(t - NR) * kCgMaxPartials + blockIdx.x] = sum;
 }
 
-// csr_spmm_dot2_k that returns early only once every column has stopped (*allDone, which block 0
-// of the batched update writes). Until then a stopped column is computed again from its unchanged
-// r: the same w, the same gamma, so the update stops it again without remembering that it had.
+template <int W, int K, int NR>
+__global__ __launch_bounds__(kSpmvThreads) void csr_spmm_dot2_k(
+    int nRows, const int32_t *__restrict__ rowPtr, const int32_t *__restrict__ colInd,
+    const float *__restrict__ val, const float *__restrict__ r, float *__restrict__ w,
+    double *__restrict__ partialsGamma, double *__restrict__ partialsDelta, const double *__restrict__ gammaOut,
+    const double *__restrict__ alphaOut, double *__restrict__ gammaPrev, double *__restrict__ alphaPrev) {
+  spmm_dot2_body<W, K, NR>(nRows, rowPtr, colInd, val, r, w, partialsGamma, partialsDelta, gammaOut, alphaOut,
+                           gammaPrev, alphaPrev);
+}
+
+// returns early only once every column has stopped (*allDone, which block 0 of the batched update
+// writes). Until then a stopped column is computed again from its unchanged r: the same w, the
+// same gamma, so the update stops it again without remembering that it had.
 template <int W, int K, int NR>
 __global__ __launch_bounds__(kSpmvThreads) void csr_spmm_dot2_stop_k(
     int nRows, const int32_t *__restrict__ rowPtr, const int32_t *__restrict__ colInd,
@@ -414,36 +415,9 @@ __global__ __launch_bounds__(kSpmvThreads) void csr_spmm_dot2_stop_k(
     double *__restrict__ partialsGamma, double *__restrict__ partialsDelta, const double *__restrict__ gammaOut,
     const double *__restrict__ alphaOut, double *__restrict__ gammaPrev, double *__restrict__ alphaPrev,
     const int *__restrict__ allDone) {
-  __shared__ double sh[2 * NR * (kSpmvThreads / 64)];
   if (*allDone) return; // uniform over the grid
-  if (gammaOut && blockIdx.x == 0 && int(threadIdx.x) < NR) {
-    gammaPrev[threadIdx.x] = gammaOut[threadIdx.x];
-    alphaPrev[threadIdx.x] = alphaOut[threadIdx.x];
-  }
-  const int lane = threadIdx.x & (W - 1);
-  const int rowsPerPass = int(gridDim.x) * (kSpmvThreads / W);
-  double acc[2 * NR]; // gamma of column j at j, delta at NR + j
-#pragma unroll
-  for (int j = 0; j < 2 * NR; ++j) acc[j] = 0.0;
-  // whole W-lane groups leave the loop together (W divides 64)
-  for (int row = (blockIdx.x * kSpmvThreads + threadIdx.x) / W; row < nRows; row += rowsPerPass) {
-    float sum[NR];
-    dev::csr_spmm_ilp_sum<W, K, NR>(row, lane, rowPtr, colInd, val, r, sum);
-    if (lane == 0) {
-      float ri[NR];
-      dev::load_row<NR>(r + int64_t(row) * NR, ri);
-      dev::store_row<NR>(w + int64_t(row) * NR, sum);
-#pragma unroll
-      for (int j = 0; j < NR; ++j) {
-        acc[j] += double(ri[j]) * double(ri[j]);
-        acc[NR + j] += double(ri[j]) * double(sum[j]);
-      }
-    }
-  }
-  const double sum = block_sum_n<kSpmvThreads / 64, 2 * NR>(acc, sh);
-  const int t = threadIdx.x; // thread j writes gamma's slab j, thread NR + j delta's
-  if (t < NR) partialsGamma[t * kCgMaxPartials + blockIdx.x] = sum;
-  else if (t < 2 * NR) partialsDelta[(t - NR) * kCgMaxPartials + blockIdx.x] = sum;
+  spmm_dot2_body<W, K, NR>(nRows, rowPtr, colInd, val, r, w, partialsGamma, partialsDelta, gammaOut, alphaOut,
+                           gammaPrev, alphaPrev);
 }
 
 // alpha = gamma / (delta - beta * (gamma / alphaPrev)), every division guarded. The product and
@@ -457,202 +431,126 @@ __device__ __forceinline__ double sr_alpha(double gamma, double delta, double be
   return guarded_div(gamma, delta - t);
 }
 
-// One pass over the five vectors: beta and alpha formed in the prologue from the two slabs and
-// the previous iteration's gamma and alpha, then per element
-//   p = fmaf(b, p, r)   s = fmaf(b, s, w)   x = fmaf(a, p, x)   r = fmaf(-a, s, r)
-// (xpay_pass, xpay_pass, axpy_pass(+a), axpy_pass(-a) in one sweep). Block 0 publishes gamma,
-// alpha and beta to places no block of this launch reads.
-__global__ __launch_bounds__(kThreads) void cg_sr_update_k(int64_t n, const double *__restrict__ partialsGamma,
-                                                           const double *__restrict__ partialsDelta, int np,
-                                                           const double *__restrict__ gammaPrev,
-                                                           const double *__restrict__ alphaPrev,
-                                                           const float *w, float *r, float *p, float *s,
-                                                           float *x, double *__restrict__ gammaOut,
-                                                           double *__restrict__ alphaOut,
-                                                           double *__restrict__ betaOut) {
+// The recurrence on one element, the only place it is written (xpay_pass, xpay_pass,
+// axpy_pass(+a), axpy_pass(-a) in one sweep) ...
+__device__ __forceinline__ void sr_elem(float b, float a, float w, float &r, float &p, float &s, float &x) {
+  p = fmaf(b, p, r);
+  s = fmaf(b, s, w);
+  x = fmaf(a, p, x);
+  r = fmaf(-a, s, r);
+}
+
+// ... on a quad whose lanes each have their own beta and alpha ...
+__device__ __forceinline__ void sr_quad(const float (&b)[4], const float (&a)[4], float4 w, float4 &r, float4 &p,
+                                        float4 &s, float4 &x) {
+  sr_elem(b[0], a[0], w.x, r.x, p.x, s.x, x.x);
+  sr_elem(b[1], a[1], w.y, r.y, p.y, s.y, x.y);
+  sr_elem(b[2], a[2], w.z, r.z, p.z, s.z, x.z);
+  sr_elem(b[3], a[3], w.w, r.w, p.w, s.w, x.w);
+}
+
+// ... and on element t of the five vectors (the tails)
+__device__ __forceinline__ void sr_elem_at(int64_t t, float b, float a, const float *w, float *r, float *p,
+                                           float *s, float *x) {
+  float rt = r[t], pt = p[t], st = s[t], xt = x[t];
+  sr_elem(b, a, w[t], rt, pt, st, xt);
+  p[t] = pt, s[t] = st, x[t] = xt, r[t] = rt;
+}
+
+// The update's prologue: gamma and delta from the two slabs, then beta and alpha from them and
+// the previous iteration's gamma and alpha; the same bits in every thread of every block
+struct SrScalars {
+  double gamma, alpha, beta;
+};
+__device__ __forceinline__ SrScalars sr_scalars(const double *__restrict__ partialsGamma,
+                                                const double *__restrict__ partialsDelta, int np,
+                                                const double *__restrict__ gammaPrev,
+                                                const double *__restrict__ alphaPrev) {
   __shared__ double sh[kThreads / 64];
   const double gamma = sum_partials<kThreads / 64>(partialsGamma, np, sh);
   const double delta = sum_partials<kThreads / 64>(partialsDelta, np, sh);
   const double beta = guarded_div(gamma, *gammaPrev);
-  const double alpha = sr_alpha(gamma, delta, beta, *alphaPrev);
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    *gammaOut = gamma;
-    *alphaOut = alpha;
-    *betaOut = beta;
-  }
-  const float b = float(beta), a = float(alpha), na = -a;
+  return {gamma, sr_alpha(gamma, delta, beta, *alphaPrev), beta};
+}
+
+// One pass over the five vectors with beta and alpha rounded to f32
+__device__ __forceinline__ void sr_pass(int64_t n, float b, float a, const float *w, float *r, float *p, float *s,
+                                        float *x) {
+  const float b4[4] = {b, b, b, b}, a4[4] = {a, a, a, a};
   const bool aw = aligned16(w), ar = aligned16(r), ap = aligned16(p), as = aligned16(s), ax = aligned16(x);
   const int64_t nq = n / 4, stride = int64_t(gridDim.x) * kThreads;
   for (int64_t k = int64_t(blockIdx.x) * kThreads + threadIdx.x; k < nq; k += stride) {
     const float4 wv = load_quad(w, k, aw);
     float4 rv = load_quad(r, k, ar), pv = load_quad(p, k, ap), sv = load_quad(s, k, as), xv = load_quad(x, k, ax);
-    pv.x = fmaf(b, pv.x, rv.x), pv.y = fmaf(b, pv.y, rv.y), pv.z = fmaf(b, pv.z, rv.z), pv.w = fmaf(b, pv.w, rv.w);
-    sv.x = fmaf(b, sv.x, wv.x), sv.y = fmaf(b, sv.y, wv.y), sv.z = fmaf(b, sv.z, wv.z), sv.w = fmaf(b, sv.w, wv.w);
-    xv.x = fmaf(a, pv.x, xv.x), xv.y = fmaf(a, pv.y, xv.y), xv.z = fmaf(a, pv.z, xv.z), xv.w = fmaf(a, pv.w, xv.w);
-    rv.x = fmaf(na, sv.x, rv.x), rv.y = fmaf(na, sv.y, rv.y), rv.z = fmaf(na, sv.z, rv.z), rv.w = fmaf(na, sv.w, rv.w);
+    sr_quad(b4, a4, wv, rv, pv, sv, xv);
     store_quad(p, k, ap, pv);
     store_quad(s, k, as, sv);
     store_quad(x, k, ax, xv);
     store_quad(r, k, ar, rv);
   }
   const int64_t t = nq * 4 + threadIdx.x;
-  if (blockIdx.x == 0 && t < n) {
-    const float rt = r[t];
-    const float pt = fmaf(b, p[t], rt), st = fmaf(b, s[t], w[t]);
-    p[t] = pt;
-    s[t] = st;
-    x[t] = fmaf(a, pt, x[t]);
-    r[t] = fmaf(na, st, rt);
-  }
+  if (blockIdx.x == 0 && t < n) sr_elem_at(t, b, a, w, r, p, s, x);
 }
 
-// cg_sr_update_k with the test after the same prologue. gamma <= *thresh ends every block before
-// it touches a vector, and block 0 stores only gamma and *done = 1. Otherwise the pass is
-// cg_sr_update_k's, and block 0 also stores *done = 0 and counts the iteration in *iters; no
-// block's path depends on done or iters.
+// The second launch: prologue, then the pass. Block 0 publishes gamma, alpha and beta to places
+// no block of this launch reads.
+__global__ __launch_bounds__(kThreads) void cg_sr_update_k(
+    int64_t n, const double *__restrict__ partialsGamma, const double *__restrict__ partialsDelta, int np,
+    const double *__restrict__ gammaPrev, const double *__restrict__ alphaPrev, const float *w, float *r,
+    float *p, float *s, float *x, double *__restrict__ gammaOut, double *__restrict__ alphaOut,
+    double *__restrict__ betaOut) {
+  const SrScalars c = sr_scalars(partialsGamma, partialsDelta, np, gammaPrev, alphaPrev);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    *gammaOut = c.gamma;
+    *alphaOut = c.alpha;
+    *betaOut = c.beta;
+  }
+  sr_pass(n, float(c.beta), float(c.alpha), w, r, p, s, x);
+}
+
+// The test between the same prologue and the same pass. gamma <= *thresh ends every block before
+// it touches a vector, and block 0 stores only gamma and *done = 1. Otherwise block 0 also stores
+// *done = 0 and counts the iteration in *iters; no block's path depends on done or iters.
 __global__ __launch_bounds__(kThreads) void cg_sr_update_stop_k(
     int64_t n, const double *__restrict__ partialsGamma, const double *__restrict__ partialsDelta, int np,
     const double *__restrict__ gammaPrev, const double *__restrict__ alphaPrev, const float *w, float *r,
     float *p, float *s, float *x, double *__restrict__ gammaOut, double *__restrict__ alphaOut,
     double *__restrict__ betaOut, const double *__restrict__ thresh, int *__restrict__ done,
     int64_t *__restrict__ iters) {
-  __shared__ double sh[kThreads / 64];
-  const double gamma = sum_partials<kThreads / 64>(partialsGamma, np, sh);
-  const double delta = sum_partials<kThreads / 64>(partialsDelta, np, sh);
-  const double beta = guarded_div(gamma, *gammaPrev);
-  const double alpha = sr_alpha(gamma, delta, beta, *alphaPrev);
-  if (gamma <= *thresh) { // the same bits, hence the same branch, in every block
+  const SrScalars c = sr_scalars(partialsGamma, partialsDelta, np, gammaPrev, alphaPrev);
+  if (c.gamma <= *thresh) { // the same bits, hence the same branch, in every block
     if (blockIdx.x == 0 && threadIdx.x == 0) {
-      *gammaOut = gamma;
+      *gammaOut = c.gamma;
       *done = 1;
     }
     return;
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) {
-    *gammaOut = gamma;
-    *alphaOut = alpha;
-    *betaOut = beta;
+    *gammaOut = c.gamma;
+    *alphaOut = c.alpha;
+    *betaOut = c.beta;
     *done = 0;
     *iters += 1;
   }
-  const float b = float(beta), a = float(alpha), na = -a;
-  const bool aw = aligned16(w), ar = aligned16(r), ap = aligned16(p), as = aligned16(s), ax = aligned16(x);
-  const int64_t nq = n / 4, stride = int64_t(gridDim.x) * kThreads;
-  for (int64_t k = int64_t(blockIdx.x) * kThreads + threadIdx.x; k < nq; k += stride) {
-    const float4 wv = load_quad(w, k, aw);
-    float4 rv = load_quad(r, k, ar), pv = load_quad(p, k, ap), sv = load_quad(s, k, as), xv = load_quad(x, k, ax);
-    pv.x = fmaf(b, pv.x, rv.x), pv.y = fmaf(b, pv.y, rv.y), pv.z = fmaf(b, pv.z, rv.z), pv.w = fmaf(b, pv.w, rv.w);
-    sv.x = fmaf(b, sv.x, wv.x), sv.y = fmaf(b, sv.y, wv.y), sv.z = fmaf(b, sv.z, wv.z), sv.w = fmaf(b, sv.w, wv.w);
-    xv.x = fmaf(a, pv.x, xv.x), xv.y = fmaf(a, pv.y, xv.y), xv.z = fmaf(a, pv.z, xv.z), xv.w = fmaf(a, pv.w, xv.w);
-    rv.x = fmaf(na, sv.x, rv.x), rv.y = fmaf(na, sv.y, rv.y), rv.z = fmaf(na, sv.z, rv.z), rv.w = fmaf(na, sv.w, rv.w);
-    store_quad(p, k, ap, pv);
-    store_quad(s, k, as, sv);
-    store_quad(x, k, ax, xv);
-    store_quad(r, k, ar, rv);
-  }
-  const int64_t t = nq * 4 + threadIdx.x;
-  if (blockIdx.x == 0 && t < n) {
-    const float rt = r[t];
-    const float pt = fmaf(b, p[t], rt), st = fmaf(b, s[t], w[t]);
-    p[t] = pt;
-    s[t] = st;
-    x[t] = fmaf(a, pt, x[t]);
-    r[t] = fmaf(na, st, rt);
-  }
+  sr_pass(n, float(c.beta), float(c.alpha), w, r, p, s, x);
 }
 
-// cg_sr_update_k for NR right-hand sides, interleaved: one pass over the n * NR elements in the
-// quad layout, every column with its own beta and alpha. A thread's quads always hold the same
-// columns (the pass stride, blocks * 256 quads, is a multiple of NR elements), so it keeps four
-// (beta, alpha) pairs in registers. The prologue sums the 2 NR slabs together: thread t holds
-// partial t of each, one butterfly per slab, one barrier, then thread j < NR adds the four wave
-// sums of gamma_j and delta_j in wave order (the bits of sum_partials), forms beta_j and alpha_j
-// as cg_sr_update_k does and leaves them, rounded to f32, in LDS for the block.
-template <int NR>
-__global__ __launch_bounds__(kThreads) void cg_sr_update_batch_k(
-    int64_t n, const double *__restrict__ partialsGamma, const double *__restrict__ partialsDelta, int np,
-    const double *__restrict__ gammaPrev, const double *__restrict__ alphaPrev, const float *w, float *r,
-    float *p, float *s, float *x, double *__restrict__ gammaOut, double *__restrict__ alphaOut,
-    double *__restrict__ betaOut) {
-  constexpr int NW = kThreads / 64;
-  __shared__ double sh[2 * NR * NW];
-  __shared__ float shB[NR], shA[NR];
-  const int tid = threadIdx.x;
-  double v[2 * NR]; // gamma of column j at j, delta at NR + j
-#pragma unroll
-  for (int j = 0; j < NR; ++j) {
-    v[j] = tid < np ? partialsGamma[j * kCgMaxPartials + tid] : 0.0;
-    v[NR + j] = tid < np ? partialsDelta[j * kCgMaxPartials + tid] : 0.0;
-  }
-#pragma unroll
-  for (int i = 0; i < 2 * NR; ++i) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v[i] += __shfl_xor(v[i], off, 64);
-  }
-  if ((tid & 63) == 0) {
-#pragma unroll
-    for (int i = 0; i < 2 * NR; ++i) sh[i * NW + (tid >> 6)] = v[i];
-  }
-  __syncthreads();
-  if (tid < NR) {
-    double gamma = sh[tid * NW], delta = sh[(NR + tid) * NW];
-#pragma unroll
-    for (int wv = 1; wv < NW; ++wv) {
-      gamma += sh[tid * NW + wv];
-      delta += sh[(NR + tid) * NW + wv];
-    }
-    const double beta = guarded_div(gamma, gammaPrev[tid]);
-    const double alpha = sr_alpha(gamma, delta, beta, alphaPrev[tid]);
-    if (blockIdx.x == 0) {
-      gammaOut[tid] = gamma;
-      alphaOut[tid] = alpha;
-      betaOut[tid] = beta;
-    }
-    shB[tid] = float(beta);
-    shA[tid] = float(alpha);
-  }
-  __syncthreads();
-  const int col0 = (4 * tid) & (NR - 1);
-  float b[4], a[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    b[i] = shB[(col0 + i) & (NR - 1)];
-    a[i] = shA[(col0 + i) & (NR - 1)];
-  }
-  const int64_t total = n * NR, nq = total / 4, stride = int64_t(gridDim.x) * kThreads;
-  for (int64_t k = int64_t(blockIdx.x) * kThreads + tid; k < nq; k += stride) {
-    const float4 wv = load_quad(w, k, true);
-    float4 rv = load_quad(r, k, true), pv = load_quad(p, k, true), sv = load_quad(s, k, true),
-           xv = load_quad(x, k, true);
-    pv.x = fmaf(b[0], pv.x, rv.x), pv.y = fmaf(b[1], pv.y, rv.y), pv.z = fmaf(b[2], pv.z, rv.z), pv.w = fmaf(b[3], pv.w, rv.w);
-    sv.x = fmaf(b[0], sv.x, wv.x), sv.y = fmaf(b[1], sv.y, wv.y), sv.z = fmaf(b[2], sv.z, wv.z), sv.w = fmaf(b[3], sv.w, wv.w);
-    xv.x = fmaf(a[0], pv.x, xv.x), xv.y = fmaf(a[1], pv.y, xv.y), xv.z = fmaf(a[2], pv.z, xv.z), xv.w = fmaf(a[3], pv.w, xv.w);
-    rv.x = fmaf(-a[0], sv.x, rv.x), rv.y = fmaf(-a[1], sv.y, rv.y), rv.z = fmaf(-a[2], sv.z, rv.z), rv.w = fmaf(-a[3], sv.w, rv.w);
-    store_quad(p, k, true, pv);
-    store_quad(s, k, true, sv);
-    store_quad(x, k, true, xv);
-    store_quad(r, k, true, rv);
-  }
-  // the total % 4 tail elements (NR = 2 with an odd n only)
-  const int64_t t = nq * 4 + tid;
-  if (blockIdx.x == 0 && t < total) {
-    const float bt = shB[t & (NR - 1)], at = shA[t & (NR - 1)];
-    const float rt = r[t];
-    const float pt = fmaf(bt, p[t], rt), st = fmaf(bt, s[t], w[t]);
-    p[t] = pt;
-    s[t] = st;
-    x[t] = fmaf(at, pt, x[t]);
-    r[t] = fmaf(-at, st, rt);
-  }
-}
-
-// cg_sr_update_batch_k with one test per column: thread j < NR also forms stop_j = gamma_j <=
-// thresh[j], the same in every block. A stopped column is frozen by a per-lane select that stores
-// back the p, s, x and r it loaded (a thread's lanes always hold the same columns); its alpha and
-// beta are not published and its iters not counted. Once every column has stopped no block passes
-// over the vectors. Block 0 stores done[j] = stop_j and *allDone = their AND.
-template <int NR>
-__global__ __launch_bounds__(kThreads) void cg_sr_update_batch_stop_k(
+// The update for NR right-hand sides, interleaved: one pass over the n * NR elements in the quad
+// layout, every column with its own beta and alpha. A thread's quads always hold the same columns
+// (the pass stride, blocks * 256 quads, is a multiple of NR elements), so it keeps four (beta,
+// alpha) pairs in registers. The prologue sums the 2 NR slabs together (wave_sums: thread t holds
+// partial t of each, one butterfly per slab, one barrier), then thread j < NR adds the four wave
+// sums of gamma_j and of delta_j in wave order (the bits of sum_partials), forms beta_j and
+// alpha_j as sr_scalars does and leaves them, rounded to f32, in LDS for the block.
+//
+// STOP adds one test per column: thread j < NR also forms stop_j = gamma_j <= thresh[j], the same
+// in every block. A stopped column is frozen by a per-lane select that stores back the p, s, x
+// and r it loaded (a thread's lanes always hold the same columns); its alpha and beta are not
+// published and its iters not counted. Once every column has stopped no block passes over the
+// vectors. Block 0 stores done[j] = stop_j and *allDone = their AND. Without STOP the last four
+// arguments are not read and shStop, never referenced, takes no LDS.
+template <int NR, bool STOP>
+__device__ __forceinline__ void sr_update_batch_body(
     int64_t n, const double *__restrict__ partialsGamma, const double *__restrict__ partialsDelta, int np,
     const double *__restrict__ gammaPrev, const double *__restrict__ alphaPrev, const float *w, float *r,
     float *p, float *s, float *x, double *__restrict__ gammaOut, double *__restrict__ alphaOut,
@@ -669,45 +567,34 @@ __global__ __launch_bounds__(kThreads) void cg_sr_update_batch_stop_k(
     v[j] = tid < np ? partialsGamma[j * kCgMaxPartials + tid] : 0.0;
     v[NR + j] = tid < np ? partialsDelta[j * kCgMaxPartials + tid] : 0.0;
   }
-#pragma unroll
-  for (int i = 0; i < 2 * NR; ++i) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v[i] += __shfl_xor(v[i], off, 64);
-  }
-  if ((tid & 63) == 0) {
-#pragma unroll
-    for (int i = 0; i < 2 * NR; ++i) sh[i * NW + (tid >> 6)] = v[i];
-  }
-  __syncthreads();
+  wave_sums<NW>(v, sh);
   if (tid < NR) {
-    double gamma = sh[tid * NW], delta = sh[(NR + tid) * NW];
-#pragma unroll
-    for (int wv = 1; wv < NW; ++wv) {
-      gamma += sh[tid * NW + wv];
-      delta += sh[(NR + tid) * NW + wv];
-    }
+    const double gamma = wave_total<NW>(sh, tid), delta = wave_total<NW>(sh, NR + tid);
     const double beta = guarded_div(gamma, gammaPrev[tid]);
     const double alpha = sr_alpha(gamma, delta, beta, alphaPrev[tid]);
-    const bool stop = gamma <= thresh[tid];
+    bool stop = false;
+    if constexpr (STOP) stop = gamma <= thresh[tid];
     if (blockIdx.x == 0) {
       gammaOut[tid] = gamma;
-      done[tid] = stop;
+      if constexpr (STOP) done[tid] = stop;
       if (!stop) {
         alphaOut[tid] = alpha;
         betaOut[tid] = beta;
-        iters[tid] += 1;
+        if constexpr (STOP) iters[tid] += 1;
       }
     }
     shB[tid] = float(beta);
     shA[tid] = float(alpha);
-    shStop[tid] = stop;
+    if constexpr (STOP) shStop[tid] = stop;
   }
   __syncthreads();
-  bool all = true;
+  if constexpr (STOP) {
+    bool all = true;
 #pragma unroll
-  for (int j = 0; j < NR; ++j) all = all && shStop[j] != 0;
-  if (blockIdx.x == 0 && tid == 0) *allDone = all;
-  if (all) return; // uniform over the grid
+    for (int j = 0; j < NR; ++j) all = all && shStop[j] != 0;
+    if (blockIdx.x == 0 && tid == 0) *allDone = all;
+    if (all) return; // uniform over the grid
+  }
   const int col0 = (4 * tid) & (NR - 1);
   float b[4], a[4];
   bool keep[4];
@@ -715,7 +602,7 @@ __global__ __launch_bounds__(kThreads) void cg_sr_update_batch_stop_k(
   for (int i = 0; i < 4; ++i) {
     b[i] = shB[(col0 + i) & (NR - 1)];
     a[i] = shA[(col0 + i) & (NR - 1)];
-    keep[i] = shStop[(col0 + i) & (NR - 1)] != 0;
+    if constexpr (STOP) keep[i] = shStop[(col0 + i) & (NR - 1)] != 0;
   }
   const int64_t total = n * NR, nq = total / 4, stride = int64_t(gridDim.x) * kThreads;
   for (int64_t k = int64_t(blockIdx.x) * kThreads + tid; k < nq; k += stride) {
@@ -723,14 +610,13 @@ __global__ __launch_bounds__(kThreads) void cg_sr_update_batch_stop_k(
     float4 rv = load_quad(r, k, true), pv = load_quad(p, k, true), sv = load_quad(s, k, true),
            xv = load_quad(x, k, true);
     const float4 r0 = rv, p0 = pv, s0 = sv, x0 = xv;
-    pv.x = fmaf(b[0], pv.x, rv.x), pv.y = fmaf(b[1], pv.y, rv.y), pv.z = fmaf(b[2], pv.z, rv.z), pv.w = fmaf(b[3], pv.w, rv.w);
-    sv.x = fmaf(b[0], sv.x, wv.x), sv.y = fmaf(b[1], sv.y, wv.y), sv.z = fmaf(b[2], sv.z, wv.z), sv.w = fmaf(b[3], sv.w, wv.w);
-    xv.x = fmaf(a[0], pv.x, xv.x), xv.y = fmaf(a[1], pv.y, xv.y), xv.z = fmaf(a[2], pv.z, xv.z), xv.w = fmaf(a[3], pv.w, xv.w);
-    rv.x = fmaf(-a[0], sv.x, rv.x), rv.y = fmaf(-a[1], sv.y, rv.y), rv.z = fmaf(-a[2], sv.z, rv.z), rv.w = fmaf(-a[3], sv.w, rv.w);
-    keep_quad(pv, p0, keep);
-    keep_quad(sv, s0, keep);
-    keep_quad(xv, x0, keep);
-    keep_quad(rv, r0, keep);
+    sr_quad(b, a, wv, rv, pv, sv, xv);
+    if constexpr (STOP) {
+      keep_quad(pv, p0, keep);
+      keep_quad(sv, s0, keep);
+      keep_quad(xv, x0, keep);
+      keep_quad(rv, r0, keep);
+    }
     store_quad(p, k, true, pv);
     store_quad(s, k, true, sv);
     store_quad(x, k, true, xv);
@@ -738,15 +624,30 @@ __global__ __launch_bounds__(kThreads) void cg_sr_update_batch_stop_k(
   }
   // the total % 4 tail elements (NR = 2 with an odd n only)
   const int64_t t = nq * 4 + tid;
-  if (blockIdx.x == 0 && t < total && !shStop[t & (NR - 1)]) {
-    const float bt = shB[t & (NR - 1)], at = shA[t & (NR - 1)];
-    const float rt = r[t];
-    const float pt = fmaf(bt, p[t], rt), st = fmaf(bt, s[t], w[t]);
-    p[t] = pt;
-    s[t] = st;
-    x[t] = fmaf(at, pt, x[t]);
-    r[t] = fmaf(-at, st, rt);
-  }
+  bool live = blockIdx.x == 0 && t < total;
+  if constexpr (STOP) live = live && !shStop[t & (NR - 1)];
+  if (live) sr_elem_at(t, shB[t & (NR - 1)], shA[t & (NR - 1)], w, r, p, s, x);
+}
+
+template <int NR>
+__global__ __launch_bounds__(kThreads) void cg_sr_update_batch_k(
+    int64_t n, const double *__restrict__ partialsGamma, const double *__restrict__ partialsDelta, int np,
+    const double *__restrict__ gammaPrev, const double *__restrict__ alphaPrev, const float *w, float *r,
+    float *p, float *s, float *x, double *__restrict__ gammaOut, double *__restrict__ alphaOut,
+    double *__restrict__ betaOut) {
+  sr_update_batch_body<NR, false>(n, partialsGamma, partialsDelta, np, gammaPrev, alphaPrev, w, r, p, s, x,
+                                  gammaOut, alphaOut, betaOut, nullptr, nullptr, nullptr, nullptr);
+}
+
+template <int NR>
+__global__ __launch_bounds__(kThreads) void cg_sr_update_batch_stop_k(
+    int64_t n, const double *__restrict__ partialsGamma, const double *__restrict__ partialsDelta, int np,
+    const double *__restrict__ gammaPrev, const double *__restrict__ alphaPrev, const float *w, float *r,
+    float *p, float *s, float *x, double *__restrict__ gammaOut, double *__restrict__ alphaOut,
+    double *__restrict__ betaOut, const double *__restrict__ thresh, int *__restrict__ done,
+    int64_t *__restrict__ iters, int *__restrict__ allDone) {
+  sr_update_batch_body<NR, true>(n, partialsGamma, partialsDelta, np, gammaPrev, alphaPrev, w, r, p, s, x,
+                                 gammaOut, alphaOut, betaOut, thresh, done, iters, allDone);
 }
 
 void check_vec(const char *what, int64_t n, const void *a, const void *b) {
@@ -870,276 +771,235 @@ void csr_spmv_dot(int nRows, const int32_t *rowPtr, const int32_t *colInd, const
   TZ_HIP_LAUNCH_CHECK();
 }
 
-void csr_spmv_dot2(int nRows, const int32_t *rowPtr, const int32_t *colInd, const float *val, const float *r,
-                   float *w, int lanes, double *partialsGamma, double *partialsDelta, const double *gammaOut,
-                   const double *alphaOut, double *gammaPrev, double *alphaPrev, void *stream) {
-  if (nRows <= 0) throw std::runtime_error("csr_spmv_dot2: nRows must be positive");
-  if (!rowPtr || !colInd || !val || !r || !w || !partialsGamma || !partialsDelta)
-    throw std::runtime_error("csr_spmv_dot2: null pointer");
-  if (partialsGamma == partialsDelta) throw std::runtime_error("csr_spmv_dot2: the two slabs must differ");
-  if (gammaOut || alphaOut || gammaPrev || alphaPrev) {
-    if (!gammaOut || !alphaOut || !gammaPrev || !alphaPrev)
-      throw std::runtime_error("csr_spmv_dot2: null pointer (the four scalars come together or not at all)");
-  }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  dispatch_ilp(lanes, "csr_spmv_dot2: lanes must be kSpmvIlp + 1, 2 or 4", [&](auto lanesPerRow, auto k) {
-    constexpr int W = decltype(lanesPerRow)::value, K = decltype(k)::value;
-    const dim3 g(unsigned(spmv_dot_partial_count(nRows, W))), b(kSpmvThreads);
-    hipLaunchKernelGGL((csr_spmv_dot2_k<W, K>), g, b, 0, s, nRows, rowPtr, colInd, val, r, w, partialsGamma,
-                       partialsDelta, gammaOut, alphaOut, gammaPrev, alphaPrev);
-  });
-  TZ_HIP_LAUNCH_CHECK();
-}
-
-void cg_sr_update(int64_t n, const double *partialsGamma, const double *partialsDelta, int np,
-                  const double *gammaPrev, const double *alphaPrev, const float *w, float *r, float *p, float *s,
-                  float *x, double *gammaOut, double *alphaOut, double *betaOut, void *stream) {
-  check_vec("cg_sr_update", n, w, r);
-  check_vec("cg_sr_update", n, p, s);
-  check_vec("cg_sr_update", n, x, x);
-  check_np("cg_sr_update", partialsGamma, np);
-  check_np("cg_sr_update", partialsDelta, np);
-  if (!gammaPrev || !alphaPrev || !gammaOut || !alphaOut || !betaOut)
-    throw std::runtime_error("cg_sr_update: null pointer");
-  // a block reads gammaPrev / alphaPrev while block 0 may already have published
-  if (gammaOut == gammaPrev || gammaOut == alphaPrev || alphaOut == gammaPrev || alphaOut == alphaPrev ||
-      betaOut == gammaPrev || betaOut == alphaPrev)
-    throw std::runtime_error("cg_sr_update: the published scalars must not alias the previous ones");
-  hipLaunchKernelGGL(cg_sr_update_k, dim3(dot_partial_count(n)), dim3(kThreads), 0,
-                     static_cast<hipStream_t>(stream), n, partialsGamma, partialsDelta, np, gammaPrev, alphaPrev,
-                     w, r, p, s, x, gammaOut, alphaOut, betaOut);
-  TZ_HIP_LAUNCH_CHECK();
-}
+// ---- the single-reduction family: every argument check once, in the two launchers
 
 namespace {
 
-// f(Int<NR>) for k = NR right-hand sides
-template <typename F> void dispatch_nrhs(int k, const char *what, F &&f) {
-  switch (k) {
-  case 2: f(Int<2>{}); break;
-  case 4: f(Int<4>{}); break;
-  case 8: f(Int<8>{}); break;
-  default: throw std::runtime_error(std::string(what) + ": k must be 2, 4 or 8 right-hand sides");
-  }
+// f(Int<NR>) for k right-hand sides, Int<1> for the single kernels: the one place k is validated
+template <typename F> void dispatch_nrhs(const char *what, bool batched, int k, F &&f) {
+  if (!batched && k == 1) f(Int<1>{});
+  else if (batched && k == 2) f(Int<2>{});
+  else if (batched && k == 4) f(Int<4>{});
+  else if (batched && k == 8) f(Int<8>{});
+  else throw std::runtime_error(std::string(what) + ": k must be 2, 4 or 8 right-hand sides");
 }
 
-void check_batch_vec(const char *what, const void *a) {
-  if (!a) throw std::runtime_error(std::string(what) + ": null pointer");
-  if (reinterpret_cast<uintptr_t>(a) % 16)
-    throw std::runtime_error(std::string(what) + ": batched vectors must be 16-byte aligned");
+const char *sr_name(bool batched, bool stop, const char *single, const char *singleStop, const char *batch,
+                    const char *batchStop) {
+  return batched ? (stop ? batchStop : batch) : (stop ? singleStop : single);
 }
-
-// k doubles at a and k doubles at b share a byte
-bool overlap(const double *a, const double *b, int k) { return a < b + k && b < a + k; }
-
-} // namespace
-
-void csr_spmm_dot2(int nRows, const int32_t *rowPtr, const int32_t *colInd, const float *val, const float *R,
-                   float *Wout, int k, int lanes, double *partialsGamma, double *partialsDelta,
-                   const double *gammaOut, const double *alphaOut, double *gammaPrev, double *alphaPrev,
-                   void *stream) {
-  if (nRows <= 0) throw std::runtime_error("csr_spmm_dot2: nRows must be positive");
-  if (k != 2 && k != 4 && k != 8) throw std::runtime_error("csr_spmm_dot2: k must be 2, 4 or 8 right-hand sides");
-  if (!rowPtr || !colInd || !val || !partialsGamma || !partialsDelta)
-    throw std::runtime_error("csr_spmm_dot2: null pointer");
-  check_batch_vec("csr_spmm_dot2", R);
-  check_batch_vec("csr_spmm_dot2", Wout);
-  if (R == Wout) throw std::runtime_error("csr_spmm_dot2: R and Wout must differ");
-  if (overlap(partialsGamma, partialsDelta, k * kCgMaxPartials))
-    throw std::runtime_error("csr_spmm_dot2: the two slab arrays must not overlap");
-  if (gammaOut || alphaOut || gammaPrev || alphaPrev) {
-    if (!gammaOut || !alphaOut || !gammaPrev || !alphaPrev)
-      throw std::runtime_error("csr_spmm_dot2: null pointer (the four scalar arrays come together or not at all)");
-  }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  dispatch_ilp(lanes, "csr_spmm_dot2: lanes must be kSpmvIlp + 1, 2 or 4", [&](auto lanesPerRow, auto depth) {
-    constexpr int W = decltype(lanesPerRow)::value, K = decltype(depth)::value;
-    dispatch_nrhs(k, "csr_spmm_dot2", [&](auto nr) {
-      constexpr int NR = decltype(nr)::value;
-      const dim3 g(unsigned(spmv_dot_partial_count(nRows, W))), b(kSpmvThreads);
-      hipLaunchKernelGGL((csr_spmm_dot2_k<W, K, NR>), g, b, 0, s, nRows, rowPtr, colInd, val, R, Wout,
-                         partialsGamma, partialsDelta, gammaOut, alphaOut, gammaPrev, alphaPrev);
-    });
-  });
-  TZ_HIP_LAUNCH_CHECK();
-}
-
-void cg_sr_update_batch(int64_t n, int k, const double *partialsGamma, const double *partialsDelta, int np,
-                        const double *gammaPrev, const double *alphaPrev, const float *W, float *R, float *P,
-                        float *S, float *X, double *gammaOut, double *alphaOut, double *betaOut, void *stream) {
-  if (n <= 0) throw std::runtime_error("cg_sr_update_batch: n must be positive");
-  if (k != 2 && k != 4 && k != 8)
-    throw std::runtime_error("cg_sr_update_batch: k must be 2, 4 or 8 right-hand sides");
-  for (const void *v : {static_cast<const void *>(W), static_cast<const void *>(R), static_cast<const void *>(P),
-                        static_cast<const void *>(S), static_cast<const void *>(X)})
-    check_batch_vec("cg_sr_update_batch", v);
-  check_np("cg_sr_update_batch", partialsGamma, np);
-  check_np("cg_sr_update_batch", partialsDelta, np);
-  if (!gammaPrev || !alphaPrev || !gammaOut || !alphaOut || !betaOut)
-    throw std::runtime_error("cg_sr_update_batch: null pointer");
-  // a block reads gammaPrev / alphaPrev while block 0 may already have published
-  for (const double *out : {gammaOut, alphaOut, betaOut})
-    if (overlap(out, gammaPrev, k) || overlap(out, alphaPrev, k))
-      throw std::runtime_error("cg_sr_update_batch: the published scalars must not alias the previous ones");
-  if (overlap(gammaOut, alphaOut, k) || overlap(gammaOut, betaOut, k) || overlap(alphaOut, betaOut, k))
-    throw std::runtime_error("cg_sr_update_batch: the three published arrays must not alias each other");
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  dispatch_nrhs(k, "cg_sr_update_batch", [&](auto nr) {
-    constexpr int NR = decltype(nr)::value;
-    hipLaunchKernelGGL((cg_sr_update_batch_k<NR>), dim3(dot_partial_count(n * k)), dim3(kThreads), 0, s, n,
-                       partialsGamma, partialsDelta, np, gammaPrev, alphaPrev, W, R, P, S, X, gammaOut, alphaOut,
-                       betaOut);
-  });
-  TZ_HIP_LAUNCH_CHECK();
-}
-
-// ---- the stopping forms: the argument checks of the kernels they extend, then their own
-
-namespace {
 
 struct Span {
   const void *p;
   size_t bytes;
 };
 
+// `count` elements at p (none at a null p)
+template <typename T> Span span(const T *p, size_t count) { return {p, p ? count * sizeof(T) : 0}; }
+
+// the two share a byte
 bool overlap(Span a, Span b) {
   const auto a0 = reinterpret_cast<uintptr_t>(a.p), b0 = reinterpret_cast<uintptr_t>(b.p);
-  return a0 < b0 + b.bytes && b0 < a0 + a.bytes;
+  return a.bytes && b.bytes && a0 < b0 + b.bytes && b0 < a0 + a.bytes;
 }
 
-// thresh is read by every block while block 0 publishes, and done / iters / all_done are stores
-// of block 0: none may share a byte with a scalar the launch reads or publishes, or with each other
-void check_stop_state(const char *what, int k, const double *gammaPrev, const double *alphaPrev,
-                      const double *gammaOut, const double *alphaOut, const double *betaOut, const double *thresh,
-                      const int *done, const int64_t *iters, const int *allDone) {
-  const std::string w(what);
-  if (!thresh || !done || !iters || (k > 1 && !allDone)) throw std::runtime_error(w + ": null pointer");
-  const size_t n = size_t(k);
-  const Span scal[5] = {{gammaPrev, 8 * n}, {alphaPrev, 8 * n}, {gammaOut, 8 * n}, {alphaOut, 8 * n}, {betaOut, 8 * n}};
-  const Span own[4] = {{thresh, 8 * n}, {done, 4 * n}, {iters, 8 * n}, {allDone, allDone ? 4u : 0u}};
+// single vectors are read in 4-byte accesses when they must be, batched ones never
+void check_sr_vecs(const char *what, bool batched, std::initializer_list<const void *> vecs) {
+  for (const void *v : vecs) {
+    if (!v) throw std::runtime_error(std::string(what) + ": null pointer");
+    if (reinterpret_cast<uintptr_t>(v) % (batched ? 16 : 4))
+      throw std::runtime_error(std::string(what) + (batched ? ": batched vectors must be 16-byte aligned"
+                                                            : ": vectors must be 4-byte aligned"));
+  }
+}
+
+void check_sr_spmv(const char *what, bool batched, bool stop, int nRows, const int32_t *rowPtr,
+                   const int32_t *colInd, const float *val, const float *r, const float *w, const SrState &st) {
+  const std::string pre = std::string(what) + ": ";
+  const size_t k = size_t(st.k);
+  const int *flag = batched ? st.all_done : st.done;
+  if (nRows <= 0) throw std::runtime_error(pre + "nRows must be positive");
+  if (!rowPtr || !colInd || !val || !r || !w || !st.partials_gamma || !st.partials_delta || (stop && !flag))
+    throw std::runtime_error(pre + "null pointer");
+  if (batched) {
+    check_sr_vecs(what, true, {r, w});
+    if (r == w) throw std::runtime_error(pre + "R and Wout must differ");
+  }
+  // a batched slab array is k whole slabs; how much of a single slab is in use only the caller
+  // knows (its partial count), so there the same pointer is refused
+  const size_t slab = batched ? k * kCgMaxPartials : 1;
+  if (overlap(span(st.partials_gamma, slab), span(st.partials_delta, slab)))
+    throw std::runtime_error(pre + "the two slab arrays must not overlap");
+  if (st.gamma || st.alpha || st.gamma_prev || st.alpha_prev) {
+    if (!st.gamma || !st.alpha || !st.gamma_prev || !st.alpha_prev)
+      throw std::runtime_error(pre + "null pointer (the four scalar arrays come together or not at all)");
+    // every block reads the flag while block 0 may already have moved the scalars
+    if (stop && (overlap(span(flag, 1), span(st.gamma_prev, k)) || overlap(span(flag, 1), span(st.alpha_prev, k))))
+      throw std::runtime_error(pre + (batched ? "all_done" : "done") + " must not alias the previous scalars");
+  }
+}
+
+void check_sr_update(const char *what, bool batched, bool stop, int64_t n, int np, const float *w, const float *r,
+                     const float *p, const float *s, const float *x, const SrState &st) {
+  const std::string pre = std::string(what) + ": ";
+  const size_t k = size_t(st.k);
+  if (n <= 0) throw std::runtime_error(pre + "n must be positive");
+  check_sr_vecs(what, batched, {w, r, p, s, x});
+  check_np(what, st.partials_gamma, np);
+  check_np(what, st.partials_delta, np);
+  if (!st.gamma_prev || !st.alpha_prev || !st.gamma || !st.alpha || !st.beta)
+    throw std::runtime_error(pre + "null pointer");
+  const Span prev[2] = {span(st.gamma_prev, k), span(st.alpha_prev, k)};
+  const Span out[3] = {span(st.gamma, k), span(st.alpha, k), span(st.beta, k)};
+  // a block reads gamma_prev / alpha_prev while block 0 may already have published
+  for (const Span &o : out)
+    if (overlap(o, prev[0]) || overlap(o, prev[1]))
+      throw std::runtime_error(pre + "the published scalars must not alias the previous ones");
+  if (overlap(out[0], out[1]) || overlap(out[0], out[2]) || overlap(out[1], out[2]))
+    throw std::runtime_error(pre + "the three published arrays must not alias each other");
+  if (!stop) return;
+  // thresh is read by every block while block 0 publishes, and done / iters / all_done are stores
+  // of block 0: none may share a byte with a scalar the launch reads or publishes, or with each other
+  if (!st.thresh || !st.done || !st.iters || (batched && !st.all_done)) throw std::runtime_error(pre + "null pointer");
+  const Span own[4] = {span(st.thresh, k), span(st.done, k), span(st.iters, k),
+                       span(st.all_done, batched ? 1 : 0)};
   for (const Span &o : own)
-    for (const Span &sc : scal)
-      if (o.bytes && overlap(o, sc))
-        throw std::runtime_error(w + ": thresh, done, iters and all_done must not alias the iteration's scalars");
+    for (const Span &sc : {prev[0], prev[1], out[0], out[1], out[2]})
+      if (overlap(o, sc))
+        throw std::runtime_error(pre + "thresh, done, iters and all_done must not alias the iteration's scalars");
   for (int i = 0; i < 4; ++i)
     for (int j = i + 1; j < 4; ++j)
-      if (own[i].bytes && own[j].bytes && overlap(own[i], own[j]))
-        throw std::runtime_error(w + ": thresh, done, iters and all_done must not alias each other");
+      if (overlap(own[i], own[j]))
+        throw std::runtime_error(pre + "thresh, done, iters and all_done must not alias each other");
+}
+
+// The public signatures say which side of an iteration a launch only reads; SrState serves both
+// launches, so it holds every pointer writable
+SrState sr_state(int k, const double *partialsGamma, const double *partialsDelta, const double *gamma,
+                 const double *alpha, const double *beta, const double *gammaPrev, const double *alphaPrev) {
+  const auto m = [](const double *p) { return const_cast<double *>(p); };
+  return {k, m(partialsGamma), m(partialsDelta), m(gamma), m(alpha), m(beta), m(gammaPrev), m(alphaPrev)};
 }
 
 } // namespace
+
+void sr_spmv_dot2(bool batched, bool stop, int nRows, const int32_t *rowPtr, const int32_t *colInd,
+                  const float *val, const float *r, float *w, int lanes, const SrState &st, void *stream) {
+  const char *what =
+      sr_name(batched, stop, "csr_spmv_dot2", "csr_spmv_dot2_stop", "csr_spmm_dot2", "csr_spmm_dot2_stop");
+  const std::string badLanes = std::string(what) + ": lanes must be kSpmvIlp + 1, 2 or 4";
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  dispatch_nrhs(what, batched, st.k, [&](auto nr) {
+    check_sr_spmv(what, batched, stop, nRows, rowPtr, colInd, val, r, w, st);
+    dispatch_ilp(lanes, badLanes.c_str(), [&](auto lanesPerRow, auto depth) {
+      constexpr int NR = decltype(nr)::value, W = decltype(lanesPerRow)::value, K = decltype(depth)::value;
+      const dim3 g(unsigned(spmv_dot_partial_count(nRows, W))), b(kSpmvThreads);
+      auto launch = [&](auto kernel, auto... flag) {
+        hipLaunchKernelGGL(kernel, g, b, 0, s, nRows, rowPtr, colInd, val, r, w, st.partials_gamma,
+                           st.partials_delta, st.gamma, st.alpha, st.gamma_prev, st.alpha_prev, flag...);
+      };
+      if constexpr (NR == 1) {
+        if (stop) launch(csr_spmv_dot2_stop_k<W, K>, st.done);
+        else launch(csr_spmv_dot2_k<W, K>);
+      } else {
+        if (stop) launch(csr_spmm_dot2_stop_k<W, K, NR>, st.all_done);
+        else launch(csr_spmm_dot2_k<W, K, NR>);
+      }
+    });
+  });
+  TZ_HIP_LAUNCH_CHECK();
+}
+
+void sr_update(bool batched, bool stop, int64_t n, int np, const float *w, float *r, float *p, float *s, float *x,
+               const SrState &st, void *stream) {
+  const char *what =
+      sr_name(batched, stop, "cg_sr_update", "cg_sr_update_stop", "cg_sr_update_batch", "cg_sr_update_batch_stop");
+  hipStream_t stm = static_cast<hipStream_t>(stream);
+  dispatch_nrhs(what, batched, st.k, [&](auto nr) {
+    constexpr int NR = decltype(nr)::value;
+    check_sr_update(what, batched, stop, n, np, w, r, p, s, x, st);
+    const dim3 g(unsigned(dot_partial_count(n * NR))), b(kThreads);
+    auto launch = [&](auto kernel, auto... stopState) {
+      hipLaunchKernelGGL(kernel, g, b, 0, stm, n, st.partials_gamma, st.partials_delta, np, st.gamma_prev,
+                         st.alpha_prev, w, r, p, s, x, st.gamma, st.alpha, st.beta, stopState...);
+    };
+    if constexpr (NR == 1) {
+      if (stop) launch(cg_sr_update_stop_k, st.thresh, st.done, st.iters);
+      else launch(cg_sr_update_k);
+    } else {
+      if (stop) launch(cg_sr_update_batch_stop_k<NR>, st.thresh, st.done, st.iters, st.all_done);
+      else launch(cg_sr_update_batch_k<NR>);
+    }
+  });
+  TZ_HIP_LAUNCH_CHECK();
+}
+
+
+// ---- the eight entry points: fill the state, call the launcher
+
+void csr_spmv_dot2(int nRows, const int32_t *rowPtr, const int32_t *colInd, const float *val, const float *r,
+                   float *w, int lanes, double *partialsGamma, double *partialsDelta, const double *gammaOut,
+                   const double *alphaOut, double *gammaPrev, double *alphaPrev, void *stream) {
+  const SrState st = sr_state(1, partialsGamma, partialsDelta, gammaOut, alphaOut, nullptr, gammaPrev, alphaPrev);
+  sr_spmv_dot2(false, false, nRows, rowPtr, colInd, val, r, w, lanes, st, stream);
+}
 
 void csr_spmv_dot2_stop(int nRows, const int32_t *rowPtr, const int32_t *colInd, const float *val, const float *r,
                         float *w, int lanes, double *partialsGamma, double *partialsDelta, const double *gammaOut,
                         const double *alphaOut, double *gammaPrev, double *alphaPrev, const int *done,
                         void *stream) {
-  if (nRows <= 0) throw std::runtime_error("csr_spmv_dot2_stop: nRows must be positive");
-  if (!rowPtr || !colInd || !val || !r || !w || !partialsGamma || !partialsDelta || !done)
-    throw std::runtime_error("csr_spmv_dot2_stop: null pointer");
-  if (partialsGamma == partialsDelta) throw std::runtime_error("csr_spmv_dot2_stop: the two slabs must differ");
-  if (gammaOut || alphaOut || gammaPrev || alphaPrev) {
-    if (!gammaOut || !alphaOut || !gammaPrev || !alphaPrev)
-      throw std::runtime_error("csr_spmv_dot2_stop: null pointer (the four scalars come together or not at all)");
-    // every block reads done while block 0 may already have moved the scalars
-    if (overlap(Span{done, 4}, Span{gammaPrev, 8}) || overlap(Span{done, 4}, Span{alphaPrev, 8}))
-      throw std::runtime_error("csr_spmv_dot2_stop: done must not alias the previous scalars");
-  }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  dispatch_ilp(lanes, "csr_spmv_dot2_stop: lanes must be kSpmvIlp + 1, 2 or 4", [&](auto lanesPerRow, auto k) {
-    constexpr int W = decltype(lanesPerRow)::value, K = decltype(k)::value;
-    const dim3 g(unsigned(spmv_dot_partial_count(nRows, W))), b(kSpmvThreads);
-    hipLaunchKernelGGL((csr_spmv_dot2_stop_k<W, K>), g, b, 0, s, nRows, rowPtr, colInd, val, r, w, partialsGamma,
-                       partialsDelta, gammaOut, alphaOut, gammaPrev, alphaPrev, done);
-  });
-  TZ_HIP_LAUNCH_CHECK();
+  SrState st = sr_state(1, partialsGamma, partialsDelta, gammaOut, alphaOut, nullptr, gammaPrev, alphaPrev);
+  st.done = const_cast<int *>(done);
+  sr_spmv_dot2(false, true, nRows, rowPtr, colInd, val, r, w, lanes, st, stream);
 }
 
-void cg_sr_update_stop(int64_t n, const double *partialsGamma, const double *partialsDelta, int np,
-                       const double *gammaPrev, const double *alphaPrev, const float *w, float *r, float *p,
-                       float *s, float *x, double *gammaOut, double *alphaOut, double *betaOut,
-                       const double *thresh, int *done, int64_t *iters, void *stream) {
-  check_vec("cg_sr_update_stop", n, w, r);
-  check_vec("cg_sr_update_stop", n, p, s);
-  check_vec("cg_sr_update_stop", n, x, x);
-  check_np("cg_sr_update_stop", partialsGamma, np);
-  check_np("cg_sr_update_stop", partialsDelta, np);
-  if (!gammaPrev || !alphaPrev || !gammaOut || !alphaOut || !betaOut)
-    throw std::runtime_error("cg_sr_update_stop: null pointer");
-  if (gammaOut == gammaPrev || gammaOut == alphaPrev || alphaOut == gammaPrev || alphaOut == alphaPrev ||
-      betaOut == gammaPrev || betaOut == alphaPrev)
-    throw std::runtime_error("cg_sr_update_stop: the published scalars must not alias the previous ones");
-  check_stop_state("cg_sr_update_stop", 1, gammaPrev, alphaPrev, gammaOut, alphaOut, betaOut, thresh, done, iters,
-                   nullptr);
-  hipLaunchKernelGGL(cg_sr_update_stop_k, dim3(dot_partial_count(n)), dim3(kThreads), 0,
-                     static_cast<hipStream_t>(stream), n, partialsGamma, partialsDelta, np, gammaPrev, alphaPrev,
-                     w, r, p, s, x, gammaOut, alphaOut, betaOut, thresh, done, iters);
-  TZ_HIP_LAUNCH_CHECK();
+void csr_spmm_dot2(int nRows, const int32_t *rowPtr, const int32_t *colInd, const float *val, const float *R,
+                   float *Wout, int k, int lanes, double *partialsGamma, double *partialsDelta,
+                   const double *gammaOut, const double *alphaOut, double *gammaPrev, double *alphaPrev,
+                   void *stream) {
+  const SrState st = sr_state(k, partialsGamma, partialsDelta, gammaOut, alphaOut, nullptr, gammaPrev, alphaPrev);
+  sr_spmv_dot2(true, false, nRows, rowPtr, colInd, val, R, Wout, lanes, st, stream);
 }
 
 void csr_spmm_dot2_stop(int nRows, const int32_t *rowPtr, const int32_t *colInd, const float *val, const float *R,
                         float *Wout, int k, int lanes, double *partialsGamma, double *partialsDelta,
                         const double *gammaOut, const double *alphaOut, double *gammaPrev, double *alphaPrev,
                         const int *allDone, void *stream) {
-  if (nRows <= 0) throw std::runtime_error("csr_spmm_dot2_stop: nRows must be positive");
-  if (k != 2 && k != 4 && k != 8)
-    throw std::runtime_error("csr_spmm_dot2_stop: k must be 2, 4 or 8 right-hand sides");
-  if (!rowPtr || !colInd || !val || !partialsGamma || !partialsDelta || !allDone)
-    throw std::runtime_error("csr_spmm_dot2_stop: null pointer");
-  check_batch_vec("csr_spmm_dot2_stop", R);
-  check_batch_vec("csr_spmm_dot2_stop", Wout);
-  if (R == Wout) throw std::runtime_error("csr_spmm_dot2_stop: R and Wout must differ");
-  if (overlap(partialsGamma, partialsDelta, k * kCgMaxPartials))
-    throw std::runtime_error("csr_spmm_dot2_stop: the two slab arrays must not overlap");
-  if (gammaOut || alphaOut || gammaPrev || alphaPrev) {
-    if (!gammaOut || !alphaOut || !gammaPrev || !alphaPrev)
-      throw std::runtime_error(
-          "csr_spmm_dot2_stop: null pointer (the four scalar arrays come together or not at all)");
-    if (overlap(Span{allDone, 4}, Span{gammaPrev, 8 * size_t(k)}) ||
-        overlap(Span{allDone, 4}, Span{alphaPrev, 8 * size_t(k)}))
-      throw std::runtime_error("csr_spmm_dot2_stop: all_done must not alias the previous scalars");
-  }
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  dispatch_ilp(lanes, "csr_spmm_dot2_stop: lanes must be kSpmvIlp + 1, 2 or 4", [&](auto lanesPerRow, auto depth) {
-    constexpr int W = decltype(lanesPerRow)::value, K = decltype(depth)::value;
-    dispatch_nrhs(k, "csr_spmm_dot2_stop", [&](auto nr) {
-      constexpr int NR = decltype(nr)::value;
-      const dim3 g(unsigned(spmv_dot_partial_count(nRows, W))), b(kSpmvThreads);
-      hipLaunchKernelGGL((csr_spmm_dot2_stop_k<W, K, NR>), g, b, 0, s, nRows, rowPtr, colInd, val, R, Wout,
-                         partialsGamma, partialsDelta, gammaOut, alphaOut, gammaPrev, alphaPrev, allDone);
-    });
-  });
-  TZ_HIP_LAUNCH_CHECK();
+  SrState st = sr_state(k, partialsGamma, partialsDelta, gammaOut, alphaOut, nullptr, gammaPrev, alphaPrev);
+  st.all_done = const_cast<int *>(allDone);
+  sr_spmv_dot2(true, true, nRows, rowPtr, colInd, val, R, Wout, lanes, st, stream);
+}
+
+void cg_sr_update(int64_t n, const double *partialsGamma, const double *partialsDelta, int np,
+                  const double *gammaPrev, const double *alphaPrev, const float *w, float *r, float *p, float *s,
+                  float *x, double *gammaOut, double *alphaOut, double *betaOut, void *stream) {
+  const SrState st = sr_state(1, partialsGamma, partialsDelta, gammaOut, alphaOut, betaOut, gammaPrev, alphaPrev);
+  sr_update(false, false, n, np, w, r, p, s, x, st, stream);
+}
+
+void cg_sr_update_stop(int64_t n, const double *partialsGamma, const double *partialsDelta, int np,
+                       const double *gammaPrev, const double *alphaPrev, const float *w, float *r, float *p,
+                       float *s, float *x, double *gammaOut, double *alphaOut, double *betaOut,
+                       const double *thresh, int *done, int64_t *iters, void *stream) {
+  SrState st = sr_state(1, partialsGamma, partialsDelta, gammaOut, alphaOut, betaOut, gammaPrev, alphaPrev);
+  st.thresh = thresh, st.done = done, st.iters = iters;
+  sr_update(false, true, n, np, w, r, p, s, x, st, stream);
+}
+
+void cg_sr_update_batch(int64_t n, int k, const double *partialsGamma, const double *partialsDelta, int np,
+                        const double *gammaPrev, const double *alphaPrev, const float *W, float *R, float *P,
+                        float *S, float *X, double *gammaOut, double *alphaOut, double *betaOut, void *stream) {
+  const SrState st = sr_state(k, partialsGamma, partialsDelta, gammaOut, alphaOut, betaOut, gammaPrev, alphaPrev);
+  sr_update(true, false, n, np, W, R, P, S, X, st, stream);
 }
 
 void cg_sr_update_batch_stop(int64_t n, int k, const double *partialsGamma, const double *partialsDelta, int np,
                              const double *gammaPrev, const double *alphaPrev, const float *W, float *R, float *P,
                              float *S, float *X, double *gammaOut, double *alphaOut, double *betaOut,
                              const double *thresh, int *done, int64_t *iters, int *allDone, void *stream) {
-  if (n <= 0) throw std::runtime_error("cg_sr_update_batch_stop: n must be positive");
-  if (k != 2 && k != 4 && k != 8)
-    throw std::runtime_error("cg_sr_update_batch_stop: k must be 2, 4 or 8 right-hand sides");
-  for (const void *v : {static_cast<const void *>(W), static_cast<const void *>(R), static_cast<const void *>(P),
-                        static_cast<const void *>(S), static_cast<const void *>(X)})
-    check_batch_vec("cg_sr_update_batch_stop", v);
-  check_np("cg_sr_update_batch_stop", partialsGamma, np);
-  check_np("cg_sr_update_batch_stop", partialsDelta, np);
-  if (!gammaPrev || !alphaPrev || !gammaOut || !alphaOut || !betaOut)
-    throw std::runtime_error("cg_sr_update_batch_stop: null pointer");
-  for (const double *out : {gammaOut, alphaOut, betaOut})
-    if (overlap(out, gammaPrev, k) || overlap(out, alphaPrev, k))
-      throw std::runtime_error("cg_sr_update_batch_stop: the published scalars must not alias the previous ones");
-  if (overlap(gammaOut, alphaOut, k) || overlap(gammaOut, betaOut, k) || overlap(alphaOut, betaOut, k))
-    throw std::runtime_error("cg_sr_update_batch_stop: the three published arrays must not alias each other");
-  check_stop_state("cg_sr_update_batch_stop", k, gammaPrev, alphaPrev, gammaOut, alphaOut, betaOut, thresh, done,
-                   iters, allDone);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  dispatch_nrhs(k, "cg_sr_update_batch_stop", [&](auto nr) {
-    constexpr int NR = decltype(nr)::value;
-    hipLaunchKernelGGL((cg_sr_update_batch_stop_k<NR>), dim3(dot_partial_count(n * k)), dim3(kThreads), 0, s, n,
-                       partialsGamma, partialsDelta, np, gammaPrev, alphaPrev, W, R, P, S, X, gammaOut, alphaOut,
-                       betaOut, thresh, done, iters, allDone);
-  });
-  TZ_HIP_LAUNCH_CHECK();
+  SrState st = sr_state(k, partialsGamma, partialsDelta, gammaOut, alphaOut, betaOut, gammaPrev, alphaPrev);
+  st.thresh = thresh, st.done = done, st.iters = iters, st.all_done = allDone;
+  sr_update(true, true, n, np, W, R, P, S, X, st, stream);
 }
 
 } // namespace kern

@@ -345,6 +345,30 @@ void cg_sr_update_batch_stop(int64_t n, int k, const double *partials_gamma, con
                              const double *gamma_prev, const double *alpha_prev, const float *W, float *R, float *P,
                              float *S, float *X, double *gamma_out, double *alpha_out, double *beta_out,
                              const double *thresh, int *done, int64_t *iters, int *all_done, void *stream);
+// ---- the eight functions above as two: what an iteration of the family keeps in device memory,
+// in one struct, and one launcher per launch. The eight fill an SrState and call these.
+/// k = 1: single slabs and scalars; k = 2, 4, 8: k slabs per array, k doubles per scalar array.
+/// The update publishes gamma, alpha and beta; the SpMV moves gamma and alpha to the prev pair.
+/// The stop state (the last four) may be null where no launch tests; all_done serves the
+/// batched form only.
+struct SrState {
+  int k = 1;
+  double *partials_gamma = nullptr, *partials_delta = nullptr;
+  double *gamma = nullptr, *alpha = nullptr, *beta = nullptr;
+  double *gamma_prev = nullptr, *alpha_prev = nullptr;
+  const double *thresh = nullptr;
+  int *done = nullptr;
+  int64_t *iters = nullptr;
+  int *all_done = nullptr;
+};
+/// csr_spmv_dot2 (batched: csr_spmm_dot2 on interleaved r and w), with `stop` its _stop form,
+/// which reads st.done (batched: st.all_done). Every argument is checked here, and an error
+/// carries the name of the function of the eight that (batched, stop) select.
+void sr_spmv_dot2(bool batched, bool stop, int nRows, const int32_t *rowPtr, const int32_t *colInd,
+                  const float *val, const float *r, float *w, int lanes, const SrState &st, void *stream);
+/// cg_sr_update (batched: cg_sr_update_batch), with `stop` its _stop form; likewise
+void sr_update(bool batched, bool stop, int64_t n, int np, const float *w, float *r, float *p, float *s, float *x,
+               const SrState &st, void *stream);
 
 /// y += alpha * x (f64)
 void axpy_f64(int64_t n, double alpha, const double *x, double *y, void *stream);

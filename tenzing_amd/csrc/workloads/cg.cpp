@@ -388,50 +388,28 @@ void ConjugateGradient::fused_p(void *s) const {
   kern::cg_fused_p(rows(), rrp_(), np_vec(), rr_(), dR_.as<float>(), dP_.as<float>(), s);
 }
 
-void ConjugateGradient::sr_spmv_dot(void *s) const {
-  if (a_.tol > 0) { // the same arguments and, per kernel, the flag the update publishes
-    if (a_.nrhs > 1)
-      kern::csr_spmm_dot2_stop(int(rows()), dRow_.as<int32_t>(), dCol_.as<int32_t>(), dVal_.as<float>(),
-                               dR_.as<float>(), dW_.as<float>(), a_.nrhs, kFusedLanes, bGamma_(), bDelta_(),
-                               bScal_(0), bScal_(1), bScal_(3), bScal_(4), stAllDone_(), s);
-    else
-      kern::csr_spmv_dot2_stop(int(rows()), dRow_.as<int32_t>(), dCol_.as<int32_t>(), dVal_.as<float>(),
-                               dR_.as<float>(), dW_.as<float>(), kFusedLanes, rrp_(), pq_(), srGamma_(),
-                               srAlpha_(), srGammaPrev_(), srAlphaPrev_(), stDone_(), s);
-    return;
-  }
+// dScal_'s layout for one right-hand side, dBatch_'s for several, and dStop_ with tol > 0
+kern::SrState ConjugateGradient::sr_state() const {
+  kern::SrState st;
+  st.k = a_.nrhs;
   if (a_.nrhs > 1) {
-    kern::csr_spmm_dot2(int(rows()), dRow_.as<int32_t>(), dCol_.as<int32_t>(), dVal_.as<float>(),
-                        dR_.as<float>(), dW_.as<float>(), a_.nrhs, kFusedLanes, bGamma_(), bDelta_(), bScal_(0),
-                        bScal_(1), bScal_(3), bScal_(4), s);
-    return;
+    st.partials_gamma = bGamma_(), st.partials_delta = bDelta_();
+    st.gamma = bScal_(0), st.alpha = bScal_(1), st.beta = bScal_(2), st.gamma_prev = bScal_(3), st.alpha_prev = bScal_(4);
+  } else {
+    st.partials_gamma = rrp_(), st.partials_delta = pq_();
+    st.gamma = srGamma_(), st.alpha = srAlpha_(), st.beta = srBeta_();
+    st.gamma_prev = srGammaPrev_(), st.alpha_prev = srAlphaPrev_();
   }
-  kern::csr_spmv_dot2(int(rows()), dRow_.as<int32_t>(), dCol_.as<int32_t>(), dVal_.as<float>(), dR_.as<float>(),
-                      dW_.as<float>(), kFusedLanes, rrp_(), pq_(), srGamma_(), srAlpha_(), srGammaPrev_(),
-                      srAlphaPrev_(), s);
+  if (a_.tol > 0) st.thresh = stThresh_(), st.done = stDone_(), st.iters = stIters_(), st.all_done = stAllDone_();
+  return st;
+}
+void ConjugateGradient::sr_spmv_dot(void *s) const {
+  kern::sr_spmv_dot2(a_.nrhs > 1, a_.tol > 0, int(rows()), dRow_.as<int32_t>(), dCol_.as<int32_t>(),
+                     dVal_.as<float>(), dR_.as<float>(), dW_.as<float>(), kFusedLanes, sr_state(), s);
 }
 void ConjugateGradient::sr_update(void *s) const {
-  if (a_.tol > 0) {
-    if (a_.nrhs > 1)
-      kern::cg_sr_update_batch_stop(rows(), a_.nrhs, bGamma_(), bDelta_(), np_spmv(), bScal_(3), bScal_(4),
-                                    dW_.as<float>(), dR_.as<float>(), dP_.as<float>(), dS_.as<float>(),
-                                    dX_.as<float>(), bScal_(0), bScal_(1), bScal_(2), stThresh_(), stDone_(),
-                                    stIters_(), stAllDone_(), s);
-    else
-      kern::cg_sr_update_stop(rows(), rrp_(), pq_(), np_spmv(), srGammaPrev_(), srAlphaPrev_(), dW_.as<float>(),
-                              dR_.as<float>(), dP_.as<float>(), dS_.as<float>(), dX_.as<float>(), srGamma_(),
-                              srAlpha_(), srBeta_(), stThresh_(), stDone_(), stIters_(), s);
-    return;
-  }
-  if (a_.nrhs > 1) {
-    kern::cg_sr_update_batch(rows(), a_.nrhs, bGamma_(), bDelta_(), np_spmv(), bScal_(3), bScal_(4),
-                             dW_.as<float>(), dR_.as<float>(), dP_.as<float>(), dS_.as<float>(), dX_.as<float>(),
-                             bScal_(0), bScal_(1), bScal_(2), s);
-    return;
-  }
-  kern::cg_sr_update(rows(), rrp_(), pq_(), np_spmv(), srGammaPrev_(), srAlphaPrev_(), dW_.as<float>(),
-                     dR_.as<float>(), dP_.as<float>(), dS_.as<float>(), dX_.as<float>(), srGamma_(), srAlpha_(),
-                     srBeta_(), s);
+  kern::sr_update(a_.nrhs > 1, a_.tol > 0, rows(), np_spmv(), dW_.as<float>(), dR_.as<float>(), dP_.as<float>(),
+                  dS_.as<float>(), dX_.as<float>(), sr_state(), s);
 }
 
 // ------------------------------------------------------------------ graph

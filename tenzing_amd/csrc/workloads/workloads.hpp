@@ -968,6 +968,7 @@ private:
   int checked(int col) const; // col, or throws
   std::shared_ptr<Graph> form_graph(bool fused) const;
   std::shared_ptr<Graph> sr_graph() const;
+  kern::SrState sr_state() const; // form sr's device state, from the layouts below
   CgArgs a_;
   CsrHost A_;
   std::vector<std::vector<float>> b_; // one per column

@@ -12,68 +12,16 @@ import functools
 import numpy as np
 import pytest
 
+from cg_kernel_helpers import SLAB,_f64, _host_scalars, _nan, _rand, _same_bits, _stream, _tree_sum
+
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-SLAB = 256  # kernels.CG_MAX_PARTIALS
 KS = [2, 4, 8]
 SECOND_PASS = {2: 150_005, 4: 75_003, 8: 37_503}
 # (gamma_prev, alpha_prev): the four guard cases of test_gpu_cg_sr_kernels.py
 GUARDS = ((0.8123, 0.37454011884736254), (0.0, 0.37454011884736254), (0.8123, 0.0), (0.0, 0.0))
-NAN = float("nan")
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _rand(shape, seed, dtype=torch.float32):
-    g = torch.Generator(device="cpu").manual_seed(seed)
-    return torch.randn(shape, generator=g, dtype=dtype).cuda()
-
-
-def _nan(n, dtype=torch.float64):
-    return torch.full((n,), NAN, dtype=dtype, device="cuda")
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int64 if t.dtype == torch.float64 else torch.int32)
-
-
-def _same_bits(a, b):
-    return a.shape == b.shape and torch.equal(_bits(a), _bits(b))
-
-
-def _f64(v):
-    return torch.tensor(np.atleast_1d(v), dtype=torch.float64, device="cuda")
-
-
-def _tree_sum(part):
-    """the order every prologue sums a slab in (kernels.sum_partials_f64): thread t of 256 holds
-    partial t (+0.0 past the count), xor butterfly over each 64, then the four groups in order"""
-    v = np.zeros(256, dtype=np.float64)
-    v[:len(part)] = part
-    v = v.reshape(4, 64)
-    lane = np.arange(64)
-    for off in (32, 16, 8, 4, 2, 1):
-        v = v + v[:, lane ^ off]
-    s = v[0, 0]
-    for w in (1, 2, 3):
-        s = s + v[w, 0]
-    return float(s)
-
-
-def _gdiv(a, b):
-    return a / b if b != 0 else 0.0
-
-
-def _host_scalars(gamma, delta, gamma_prev, alpha_prev):
-    """beta and alpha as the recurrence defines them, in IEEE f64 (Python floats: the product
-    and the difference round separately)"""
-    beta = _gdiv(gamma, gamma_prev)
-    alpha = _gdiv(gamma, delta - beta * _gdiv(gamma, alpha_prev))
-    return beta, alpha
 
 
 @functools.lru_cache(maxsize=None)

@@ -8,90 +8,14 @@ layout."""
 import numpy as np
 import pytest
 
+from cg_kernel_helpers import (SLAB, _check_dot, _f64, _host_scalars, _misaligned, _nan_slab, _rand, _same_bits,
+                               _stream, _tree_sum)
+
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
 SIZES = [1, 63, 64, 65, 257, 1037, 300_007]
-SLAB = 256  # kernels.CG_MAX_PARTIALS
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _rand(n, seed, dtype=torch.float32):
-    g = torch.Generator(device="cpu").manual_seed(seed)
-    return torch.randn(n, generator=g, dtype=dtype).cuda()
-
-
-def _nan_slab():
-    return torch.full((SLAB + 8,), float("nan"), dtype=torch.float64, device="cuda")
-
-
-def _bits(t):
-    return t.view(torch.int64 if t.dtype == torch.float64 else torch.int32)
-
-
-def _same_bits(a, b):
-    return torch.equal(_bits(a), _bits(b))
-
-
-def _tree_sum(part):
-    """the order every prologue sums a slab in (kernels.sum_partials_f64): thread t of 256 holds
-    partial t (+0.0 past the count), xor butterfly over each 64, then the four groups in order"""
-    v = np.zeros(256, dtype=np.float64)
-    v[:len(part)] = part
-    v = v.reshape(4, 64)
-    lane = np.arange(64)
-    for off in (32, 16, 8, 4, 2, 1):
-        v = v + v[:, lane ^ off]
-    s = v[0, 0]
-    for w in (1, 2, 3):
-        s = s + v[w, 0]
-    return float(s)
-
-
-def _misaligned(t):
-    """a copy of t that starts 4 bytes past a 16-byte boundary"""
-    buf = torch.empty(t.numel() + 4, dtype=t.dtype, device="cuda")
-    assert buf.data_ptr() % 16 == 0
-    out = buf[1:1 + t.numel()]
-    out.copy_(t)
-    assert out.data_ptr() % 16 == 4
-    return out
-
-
-def _check_dot(part, n_used, u, v, n):
-    """partials summed in index order on the host against the f64 dot product: the only error
-    is the n - 1 f64 additions (the products are exact); x 2 for the reference's own rounding"""
-    p = part.cpu().numpy()
-    assert not np.isnan(p[:n_used]).any(), "a partial slot in use was not written"
-    assert np.isnan(p[n_used:]).all(), "a slot past the documented count was touched"
-    s = 0.0
-    for x in p[:n_used]:
-        s += float(x)
-    ud, vd = u.double(), v.double()
-    ref = torch.dot(ud, vd).item()
-    bound = 2.0 * (n - 1) * 2.0 ** -53 * (ud * vd).abs().sum().item()
-    print(f"dot n={n}: |err|={abs(s - ref):.3e} bound={bound:.3e}")
-    assert abs(s - ref) <= bound
-
-
-def _f64(v):
-    return torch.tensor([v], dtype=torch.float64, device="cuda")
-
-
-def _gdiv(a, b):
-    return a / b if b != 0 else 0.0
-
-
-def _host_scalars(gamma, delta, gamma_prev, alpha_prev):
-    """beta and alpha as the recurrence defines them, in IEEE f64 (Python floats: the product
-    and the difference round separately)"""
-    beta = _gdiv(gamma, gamma_prev)
-    alpha = _gdiv(gamma, delta - beta * _gdiv(gamma, alpha_prev))
-    return beta, alpha
 
 
 @pytest.mark.parametrize("n,bw", [(50, 8), (257, 16), (1037, 1037), (70_001, 16)])

@@ -11,22 +11,17 @@ SpMV 70 001 rows, the smallest ragged second pass of 4 lanes per row."""
 import numpy as np
 import pytest
 
-from test_gpu_cg_batch_kernels import KS, SECOND_PASS, _matrix, _same_bits, _slabs
-from test_gpu_cg_sr_kernels import SLAB, _misaligned, _rand, _stream, _tree_sum
+from cg_kernel_helpers import NAN, SLAB, _f64, _misaligned, _nan, _rand, _same_bits, _stream, _tree_sum
+from test_gpu_cg_batch_kernels import KS, SECOND_PASS, _matrix, _slabs
 
 pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
-NAN = float("nan")
 INF = float("inf")
 SIZES = [1, 63, 65, 1038, 300_007]  # n % 4 = 1, 3, 1, 2, 3
 GP0, AP0 = 0.8123, 0.37454011884736254  # gamma_prev, alpha_prev: the generic case of the parents' tests
 DONE0, ITERS0 = 7, 41  # what done and iters hold before a launch
-
-
-def _f64(v):
-    return torch.tensor(np.atleast_1d(v), dtype=torch.float64, device="cuda")
 
 
 def _i32(v):
@@ -35,10 +30,6 @@ def _i32(v):
 
 def _i64(v):
     return torch.tensor(np.atleast_1d(v), dtype=torch.int64, device="cuda")
-
-
-def _nan(n, dtype=torch.float64):
-    return torch.full((n,), NAN, dtype=dtype, device="cuda")
 
 
 def _ptrs(ts):
