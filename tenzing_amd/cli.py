@@ -60,7 +60,8 @@ def _build_workload(a, ctrl, device, setup):
         return g, {"halo": h, "spmv": s}
     if a.workload == "cg":
         c, g = build_cg(CgConfig(m=a.cg_m, form=a.cg_form, matrix=a.cg_matrix, nrhs=a.cg_nrhs,
-                                 tol=a.cg_tol), ctrl, device, setup)
+                                 tol=a.cg_tol, precond=a.cg_precond, diag_scale=a.cg_diag_scale),
+                        ctrl, device, setup)
         return g, {"cg": c}
     if a.workload == "noop":
         # reference test/test_noop_graph.cpp: Start -> op1 -> Finish (here: `--noop-width`
@@ -224,7 +225,7 @@ _WORKLOAD_KEYS = ("workload", "noop_width", "streams", "halo_n", "nq", "ghost", 
                   "stencil", "rank_grid",
                   "spmv_m", "spmv_matrix", "spmv_form", "spmv_transport", "spmv_library",
                   "spmv_distribute", "cg_m", "cg_form", "cg_matrix", "cg_nrhs", "cg_tol",
-                  "cg_max_iters", "cg_check_iters",
+                  "cg_max_iters", "cg_check_iters", "cg_precond", "cg_diag_scale",
                   "cu_partition", "stream_priorities")
 
 
@@ -337,10 +338,12 @@ def cmd_run(a) -> int:
         ok &= out["spmv_max_rel_err"] < 1e-4
     if "cg" in wl:
         # x after cg_check_iters iterations against the same iterations in f64 on the host
-        # (the maximum over the right-hand sides)
+        # (the maximum over the right-hand sides); with cg_precond jacobi the host model is the
+        # recurrence preconditioned by the same dinv
         cols = range(w.cg_nrhs)
         out["cg_check_iters"] = w.cg_check_iters
         out["cg_nrhs"] = w.cg_nrhs
+        out["cg_precond"] = w.cg_precond
         out["cg_max_rel_err"] = max(wl["cg"].check(w.cg_check_iters, j) for j in cols)
         ok &= out["cg_max_rel_err"] < 1e-4
         # the true residual ||b - A x|| / ||b|| of that x: the same quantity in every form
@@ -572,6 +575,12 @@ def _parser() -> argparse.ArgumentParser:
                         "r.r <= tol^2 b.b and freeze it; `search` times full iterations (the test "
                         "disarmed), `run` also solves and reports cg_iterations, cg_converged and "
                         "the solve's cg_residual. 0: no test, the kernels without it")
+    s.add_argument("--cg-precond", default="none", choices=["none", "jacobi"],
+                   help="cg (jacobi needs --cg-form sr and --cg-nrhs 1): precondition the "
+                        "single-reduction recurrence with diag(A), still two launches per iteration")
+    s.add_argument("--cg-diag-scale", type=int, default=0,
+                   help="cg: pose the same problem in badly chosen units, (S A S) y = S b with "
+                        "S = diag(2^e), e uniform in [-N, N] (0..8; 0: the matrix as it is)")
     s.add_argument("--cg-max-iters", type=int, default=1000,
                    help="cg with --cg-tol, `run`: iterations the solve may launch")
     s.add_argument("--cg-check-iters", type=int, default=25,

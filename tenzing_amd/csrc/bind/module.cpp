@@ -1196,6 +1196,8 @@ PYBIND11_MODULE(_tz, m) {
       .def_readwrite("nrhs", &CgArgs::nrhs)
       .def_readwrite("rhs_first", &CgArgs::rhs_first)
       .def_readwrite("tol", &CgArgs::tol)
+      .def_readwrite("precond", &CgArgs::precond)
+      .def_readwrite("diag_scale", &CgArgs::diag_scale)
       .def_readwrite("prefix", &CgArgs::prefix)
       .def_readwrite("rank", &CgArgs::rank)
       .def_readwrite("size", &CgArgs::size)
@@ -1220,6 +1222,12 @@ PYBIND11_MODULE(_tz, m) {
         .def("r", [f32](const ConjugateGradient &c, int col) { return f32(c.r(col)); }, py::arg("col") = 0)
         .def("p", [f32](const ConjugateGradient &c, int col) { return f32(c.p(col)); }, py::arg("col") = 0)
         .def("b", [f32](const ConjugateGradient &c, int col) { return f32(c.b(col)); }, py::arg("col") = 0)
+        .def("u", [f32](const ConjugateGradient &c, int col) { return f32(c.u(col)); }, py::arg("col") = 0,
+             "precond jacobi: the stored u = f32(dinv * r)")
+        .def("dinv", [f32](const ConjugateGradient &c) { return f32(c.dinv()); },
+             "precond jacobi: dinv[i] = 1.0f / a_ii")
+        .def("scale", [f32](const ConjugateGradient &c) { return f32(c.scale()); },
+             "the diagonal of S (diag_scale): powers of two, all 1 with diag_scale = 0")
         .def("rr", &ConjugateGradient::rr, py::arg("col") = 0,
              "r . r of the current residual (f64, the kernels' summation order)")
         .def("check", &ConjugateGradient::check, py::arg("k"), py::arg("col") = 0,
@@ -1461,6 +1469,47 @@ PYBIND11_MODULE(_tz, m) {
      py::arg("alpha_prev"), py::arg("w"), py::arg("r"), py::arg("p"), py::arg("s"), py::arg("x"),
      py::arg("gamma_out"), py::arg("alpha_out"), py::arg("beta_out"), py::arg("thresh"), py::arg("done"),
      py::arg("iters"), py::arg("stream") = 0);
+  k.def("pcg_spmv_dot3", [](int n, uintptr_t rp, uintptr_t ci, uintptr_t v, uintptr_t r, uintptr_t u, uintptr_t w,
+                            int lanes, uintptr_t pg, uintptr_t pd, uintptr_t pr, uintptr_t gOut, uintptr_t aOut,
+                            uintptr_t gPrev, uintptr_t aPrev, uintptr_t s) {
+    kern::pcg_spmv_dot3(n, as<ci32>(rp), as<ci32>(ci), as<cf>(v), as<cf>(r), as<cf>(u), as<float>(w), lanes,
+                        as<double>(pg), as<double>(pd), as<double>(pr), as<cd>(gOut), as<cd>(aOut),
+                        as<double>(gPrev), as<double>(aPrev), P(s));
+  }, py::arg("n_rows"), py::arg("row_ptr"), py::arg("col_ind"), py::arg("val"), py::arg("r"), py::arg("u"),
+     py::arg("w"), py::arg("lanes"), py::arg("partials_gamma"), py::arg("partials_delta"), py::arg("partials_rho"),
+     py::arg("gamma_out") = 0, py::arg("alpha_out") = 0, py::arg("gamma_prev") = 0, py::arg("alpha_prev") = 0,
+     py::arg("stream") = 0);
+  k.def("pcg_spmv_dot3_stop", [](int n, uintptr_t rp, uintptr_t ci, uintptr_t v, uintptr_t r, uintptr_t u,
+                                 uintptr_t w, int lanes, uintptr_t pg, uintptr_t pd, uintptr_t pr, uintptr_t gOut,
+                                 uintptr_t aOut, uintptr_t gPrev, uintptr_t aPrev, uintptr_t done, uintptr_t s) {
+    kern::pcg_spmv_dot3_stop(n, as<ci32>(rp), as<ci32>(ci), as<cf>(v), as<cf>(r), as<cf>(u), as<float>(w), lanes,
+                             as<double>(pg), as<double>(pd), as<double>(pr), as<cd>(gOut), as<cd>(aOut),
+                             as<double>(gPrev), as<double>(aPrev), as<const int>(done), P(s));
+  }, py::arg("n_rows"), py::arg("row_ptr"), py::arg("col_ind"), py::arg("val"), py::arg("r"), py::arg("u"),
+     py::arg("w"), py::arg("lanes"), py::arg("partials_gamma"), py::arg("partials_delta"), py::arg("partials_rho"),
+     py::arg("gamma_out"), py::arg("alpha_out"), py::arg("gamma_prev"), py::arg("alpha_prev"), py::arg("done"),
+     py::arg("stream") = 0);
+  k.def("pcg_update", [](int64_t n, uintptr_t pg, uintptr_t pd, int np, uintptr_t gPrev, uintptr_t aPrev,
+                         uintptr_t w, uintptr_t dinv, uintptr_t r, uintptr_t p, uintptr_t sv, uintptr_t x,
+                         uintptr_t u, uintptr_t gOut, uintptr_t aOut, uintptr_t bOut, uintptr_t s) {
+    kern::pcg_update(n, as<cd>(pg), as<cd>(pd), np, as<cd>(gPrev), as<cd>(aPrev), as<cf>(w), as<cf>(dinv),
+                     as<float>(r), as<float>(p), as<float>(sv), as<float>(x), as<float>(u), as<double>(gOut),
+                     as<double>(aOut), as<double>(bOut), P(s));
+  }, py::arg("n"), py::arg("partials_gamma"), py::arg("partials_delta"), py::arg("np"), py::arg("gamma_prev"),
+     py::arg("alpha_prev"), py::arg("w"), py::arg("dinv"), py::arg("r"), py::arg("p"), py::arg("s"), py::arg("x"),
+     py::arg("u"), py::arg("gamma_out"), py::arg("alpha_out"), py::arg("beta_out"), py::arg("stream") = 0);
+  k.def("pcg_update_stop", [](int64_t n, uintptr_t pg, uintptr_t pd, int np, uintptr_t gPrev, uintptr_t aPrev,
+                              uintptr_t w, uintptr_t dinv, uintptr_t r, uintptr_t p, uintptr_t sv, uintptr_t x,
+                              uintptr_t u, uintptr_t gOut, uintptr_t aOut, uintptr_t bOut, uintptr_t pr,
+                              uintptr_t thresh, uintptr_t done, uintptr_t iters, uintptr_t s) {
+    kern::pcg_update_stop(n, as<cd>(pg), as<cd>(pd), np, as<cd>(gPrev), as<cd>(aPrev), as<cf>(w), as<cf>(dinv),
+                          as<float>(r), as<float>(p), as<float>(sv), as<float>(x), as<float>(u), as<double>(gOut),
+                          as<double>(aOut), as<double>(bOut), as<cd>(pr), as<cd>(thresh), as<int>(done),
+                          as<int64_t>(iters), P(s));
+  }, py::arg("n"), py::arg("partials_gamma"), py::arg("partials_delta"), py::arg("np"), py::arg("gamma_prev"),
+     py::arg("alpha_prev"), py::arg("w"), py::arg("dinv"), py::arg("r"), py::arg("p"), py::arg("s"), py::arg("x"),
+     py::arg("u"), py::arg("gamma_out"), py::arg("alpha_out"), py::arg("beta_out"), py::arg("partials_rho"),
+     py::arg("thresh"), py::arg("done"), py::arg("iters"), py::arg("stream") = 0);
   k.def("csr_spmm_dot2_stop", [](int n, uintptr_t rp, uintptr_t ci, uintptr_t v, uintptr_t r, uintptr_t w,
                                  int nrhs, int lanes, uintptr_t pg, uintptr_t pd, uintptr_t gOut, uintptr_t aOut,
                                  uintptr_t gPrev, uintptr_t aPrev, uintptr_t allDone, uintptr_t s) {

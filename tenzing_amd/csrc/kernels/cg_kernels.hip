@@ -3,7 +3,8 @@
 // kernels (SpMV + two dots, one update of p, s, x and r), those two also for 2, 4 or 8 interleaved
 // right-hand sides, and all four again with a convergence test decided on the device (*_stop):
 // eight entry points over four bodies, a stopping one being its test in front of its parent's
-// body. Not in the reference.
+// body; and the Jacobi-preconditioned pair of the single right-hand side (pcg_*), which shares
+// those bodies' arithmetic. Not in the reference.
 //
 // Vectors are f32; dot products accumulate in f64 (the product of two f32 values is exact in
 // f64); every scalar (rr, alpha, beta) is an f64 in device memory, so no launch argument carries
@@ -268,12 +269,17 @@ __global__ __launch_bounds__(kSpmvThreads) void csr_spmv_dot_k(int nRows, const 
 // gamma and delta. Block 0 also moves the scalars the previous update published into the places
 // the next update reads (gammaOut may be null): this launch lies between their writer and their
 // next reader, and nothing in it reads either side.
-template <int W, int K>
+//
+// PC is the Jacobi-preconditioned form (u = dinv o r is a stored vector): w = A u, gamma = r . u,
+// delta = u . w and a third slab, rho = r . r, which only the stopping test reads. Without PC, u
+// and partialsRho are not read.
+template <int W, int K, bool PC>
 __device__ __forceinline__ void spmv_dot2_body(
     int nRows, const int32_t *__restrict__ rowPtr, const int32_t *__restrict__ colInd,
-    const float *__restrict__ val, const float *__restrict__ r, float *__restrict__ w,
-    double *__restrict__ partialsGamma, double *__restrict__ partialsDelta, const double *__restrict__ gammaOut,
-    const double *__restrict__ alphaOut, double *__restrict__ gammaPrev, double *__restrict__ alphaPrev) {
+    const float *__restrict__ val, const float *__restrict__ r, const float *__restrict__ u,
+    float *__restrict__ w, double *__restrict__ partialsGamma, double *__restrict__ partialsDelta,
+    double *__restrict__ partialsRho, const double *__restrict__ gammaOut, const double *__restrict__ alphaOut,
+    double *__restrict__ gammaPrev, double *__restrict__ alphaPrev) {
   __shared__ double sh[kSpmvThreads / 64];
   if (gammaOut && blockIdx.x == 0 && threadIdx.x == 0) {
     *gammaPrev = *gammaOut;
@@ -281,15 +287,22 @@ __device__ __forceinline__ void spmv_dot2_body(
   }
   const int lane = threadIdx.x & (W - 1);
   const int rowsPerPass = int(gridDim.x) * (kSpmvThreads / W);
-  double accG = 0.0, accD = 0.0;
+  double accG = 0.0, accD = 0.0, accR = 0.0;
   // whole W-lane groups leave the loop together (W divides 64)
   for (int row = (blockIdx.x * kSpmvThreads + threadIdx.x) / W; row < nRows; row += rowsPerPass) {
-    const float sum = dev::csr_spmv_ilp_sum<W, K>(row, lane, rowPtr, colInd, val, r);
+    const float sum = dev::csr_spmv_ilp_sum<W, K>(row, lane, rowPtr, colInd, val, PC ? u : r);
     if (lane == 0) {
       const double ri = double(r[row]);
       w[row] = sum;
-      accG += ri * ri;
-      accD += ri * double(sum);
+      if constexpr (PC) {
+        const double ui = double(u[row]);
+        accG += ri * ui;
+        accD += ui * double(sum);
+        accR += ri * ri;
+      } else {
+        accG += ri * ri;
+        accD += ri * double(sum);
+      }
     }
   }
   const double g = block_sum<kSpmvThreads / 64>(accG, sh);
@@ -297,6 +310,10 @@ __device__ __forceinline__ void spmv_dot2_body(
   if (threadIdx.x == 0) {
     partialsGamma[blockIdx.x] = g;
     partialsDelta[blockIdx.x] = d;
+  }
+  if constexpr (PC) {
+    const double rho = block_sum<kSpmvThreads / 64>(accR, sh);
+    if (threadIdx.x == 0) partialsRho[blockIdx.x] = rho;
   }
 }
 
@@ -306,8 +323,8 @@ __global__ __launch_bounds__(kSpmvThreads) void csr_spmv_dot2_k(
     const float *__restrict__ val, const float *__restrict__ r, float *__restrict__ w,
     double *__restrict__ partialsGamma, double *__restrict__ partialsDelta, const double *__restrict__ gammaOut,
     const double *__restrict__ alphaOut, double *__restrict__ gammaPrev, double *__restrict__ alphaPrev) {
-  spmv_dot2_body<W, K>(nRows, rowPtr, colInd, val, r, w, partialsGamma, partialsDelta, gammaOut, alphaOut,
-                       gammaPrev, alphaPrev);
+  spmv_dot2_body<W, K, false>(nRows, rowPtr, colInd, val, r, nullptr, w, partialsGamma, partialsDelta, nullptr,
+                              gammaOut, alphaOut, gammaPrev, alphaPrev);
 }
 
 template <int W, int K>
@@ -318,8 +335,31 @@ __global__ __launch_bounds__(kSpmvThreads) void csr_spmv_dot2_stop_k(
     const double *__restrict__ alphaOut, double *__restrict__ gammaPrev, double *__restrict__ alphaPrev,
     const int *__restrict__ done) {
   if (*done) return; // uniform over the grid
-  spmv_dot2_body<W, K>(nRows, rowPtr, colInd, val, r, w, partialsGamma, partialsDelta, gammaOut, alphaOut,
-                       gammaPrev, alphaPrev);
+  spmv_dot2_body<W, K, false>(nRows, rowPtr, colInd, val, r, nullptr, w, partialsGamma, partialsDelta, nullptr,
+                              gammaOut, alphaOut, gammaPrev, alphaPrev);
+}
+
+template <int W, int K>
+__global__ __launch_bounds__(kSpmvThreads) void pcg_spmv_dot3_k(
+    int nRows, const int32_t *__restrict__ rowPtr, const int32_t *__restrict__ colInd,
+    const float *__restrict__ val, const float *__restrict__ r, const float *__restrict__ u,
+    float *__restrict__ w, double *__restrict__ partialsGamma, double *__restrict__ partialsDelta,
+    double *__restrict__ partialsRho, const double *__restrict__ gammaOut, const double *__restrict__ alphaOut,
+    double *__restrict__ gammaPrev, double *__restrict__ alphaPrev) {
+  spmv_dot2_body<W, K, true>(nRows, rowPtr, colInd, val, r, u, w, partialsGamma, partialsDelta, partialsRho,
+                             gammaOut, alphaOut, gammaPrev, alphaPrev);
+}
+
+template <int W, int K>
+__global__ __launch_bounds__(kSpmvThreads) void pcg_spmv_dot3_stop_k(
+    int nRows, const int32_t *__restrict__ rowPtr, const int32_t *__restrict__ colInd,
+    const float *__restrict__ val, const float *__restrict__ r, const float *__restrict__ u,
+    float *__restrict__ w, double *__restrict__ partialsGamma, double *__restrict__ partialsDelta,
+    double *__restrict__ partialsRho, const double *__restrict__ gammaOut, const double *__restrict__ alphaOut,
+    double *__restrict__ gammaPrev, double *__restrict__ alphaPrev, const int *__restrict__ done) {
+  if (*done) return; // uniform over the grid
+  spmv_dot2_body<W, K, true>(nRows, rowPtr, colInd, val, r, u, w, partialsGamma, partialsDelta, partialsRho,
+                             gammaOut, alphaOut, gammaPrev, alphaPrev);
 }
 
 // N block_sums behind one barrier, in two steps. wave_sums: the same butterfly per value, then
@@ -433,8 +473,10 @@ __device__ __forceinline__ double sr_alpha(double gamma, double delta, double be
 
 // The recurrence on one element, the only place it is written (xpay_pass, xpay_pass,
 // axpy_pass(+a), axpy_pass(-a) in one sweep) ...
-__device__ __forceinline__ void sr_elem(float b, float a, float w, float &r, float &p, float &s, float &x) {
-  p = fmaf(b, p, r);
+// z is what p is built from: r itself, or the preconditioned residual u = dinv o r.
+__device__ __forceinline__ void sr_elem(float b, float a, float w, float z, float &r, float &p, float &s,
+                                        float &x) {
+  p = fmaf(b, p, z);
   s = fmaf(b, s, w);
   x = fmaf(a, p, x);
   r = fmaf(-a, s, r);
@@ -443,17 +485,17 @@ __device__ __forceinline__ void sr_elem(float b, float a, float w, float &r, flo
 // ... on a quad whose lanes each have their own beta and alpha ...
 __device__ __forceinline__ void sr_quad(const float (&b)[4], const float (&a)[4], float4 w, float4 &r, float4 &p,
                                         float4 &s, float4 &x) {
-  sr_elem(b[0], a[0], w.x, r.x, p.x, s.x, x.x);
-  sr_elem(b[1], a[1], w.y, r.y, p.y, s.y, x.y);
-  sr_elem(b[2], a[2], w.z, r.z, p.z, s.z, x.z);
-  sr_elem(b[3], a[3], w.w, r.w, p.w, s.w, x.w);
+  sr_elem(b[0], a[0], w.x, r.x, r.x, p.x, s.x, x.x);
+  sr_elem(b[1], a[1], w.y, r.y, r.y, p.y, s.y, x.y);
+  sr_elem(b[2], a[2], w.z, r.z, r.z, p.z, s.z, x.z);
+  sr_elem(b[3], a[3], w.w, r.w, r.w, p.w, s.w, x.w);
 }
 
 // ... and on element t of the five vectors (the tails)
 __device__ __forceinline__ void sr_elem_at(int64_t t, float b, float a, const float *w, float *r, float *p,
                                            float *s, float *x) {
   float rt = r[t], pt = p[t], st = s[t], xt = x[t];
-  sr_elem(b, a, w[t], rt, pt, st, xt);
+  sr_elem(b, a, w[t], rt, rt, pt, st, xt);
   p[t] = pt, s[t] = st, x[t] = xt, r[t] = rt;
 }
 
@@ -533,6 +575,94 @@ __global__ __launch_bounds__(kThreads) void cg_sr_update_stop_k(
     *iters += 1;
   }
   sr_pass(n, float(c.beta), float(c.alpha), w, r, p, s, x);
+}
+
+// ---- The Jacobi-preconditioned update. u = dinv o r is a stored vector that this launch keeps
+// equal to f32(dinv[i] * r[i]) bit for bit: a rounded product of its own, kept from contraction
+// into the fmaf that follows it as sr_alpha keeps its product. The old u is recomputed from the
+// dinv and r the pass loads anyway (the same bits as the stored one) and not read back: 44 bytes
+// per row instead of 48.
+__device__ __forceinline__ float pcg_apply(float dinv, float r) {
+  float u = dinv * r;
+  asm volatile("" : "+v"(u));
+  return u;
+}
+
+__device__ __forceinline__ void pcg_elem(float b, float a, float w, float dinv, float &r, float &p, float &s,
+                                         float &x, float &u) {
+  sr_elem(b, a, w, pcg_apply(dinv, r), r, p, s, x);
+  u = pcg_apply(dinv, r);
+}
+
+// sr_pass with the preconditioner: one pass over w, dinv, r, p, s, x and u in the same layout
+__device__ __forceinline__ void pcg_pass(int64_t n, float b, float a, const float *w, const float *dinv, float *r,
+                                         float *p, float *s, float *x, float *u) {
+  const bool aw = aligned16(w), ad = aligned16(dinv), ar = aligned16(r), ap = aligned16(p), as = aligned16(s),
+             ax = aligned16(x), au = aligned16(u);
+  const int64_t nq = n / 4, stride = int64_t(gridDim.x) * kThreads;
+  for (int64_t k = int64_t(blockIdx.x) * kThreads + threadIdx.x; k < nq; k += stride) {
+    const float4 wv = load_quad(w, k, aw), dv = load_quad(dinv, k, ad);
+    float4 rv = load_quad(r, k, ar), pv = load_quad(p, k, ap), sv = load_quad(s, k, as), xv = load_quad(x, k, ax);
+    float4 uv;
+    pcg_elem(b, a, wv.x, dv.x, rv.x, pv.x, sv.x, xv.x, uv.x);
+    pcg_elem(b, a, wv.y, dv.y, rv.y, pv.y, sv.y, xv.y, uv.y);
+    pcg_elem(b, a, wv.z, dv.z, rv.z, pv.z, sv.z, xv.z, uv.z);
+    pcg_elem(b, a, wv.w, dv.w, rv.w, pv.w, sv.w, xv.w, uv.w);
+    store_quad(p, k, ap, pv);
+    store_quad(s, k, as, sv);
+    store_quad(x, k, ax, xv);
+    store_quad(r, k, ar, rv);
+    store_quad(u, k, au, uv);
+  }
+  const int64_t t = nq * 4 + threadIdx.x;
+  if (blockIdx.x == 0 && t < n) {
+    float rt = r[t], pt = p[t], st = s[t], xt = x[t], ut;
+    pcg_elem(b, a, w[t], dinv[t], rt, pt, st, xt, ut);
+    p[t] = pt, s[t] = st, x[t] = xt, r[t] = rt, u[t] = ut;
+  }
+}
+
+// cg_sr_update_k with gamma = r . u and delta = u . (A u) in the two slabs
+__global__ __launch_bounds__(kThreads) void pcg_update_k(
+    int64_t n, const double *__restrict__ partialsGamma, const double *__restrict__ partialsDelta, int np,
+    const double *__restrict__ gammaPrev, const double *__restrict__ alphaPrev, const float *w, const float *dinv,
+    float *r, float *p, float *s, float *x, float *u, double *__restrict__ gammaOut, double *__restrict__ alphaOut,
+    double *__restrict__ betaOut) {
+  const SrScalars c = sr_scalars(partialsGamma, partialsDelta, np, gammaPrev, alphaPrev);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    *gammaOut = c.gamma;
+    *alphaOut = c.alpha;
+    *betaOut = c.beta;
+  }
+  pcg_pass(n, float(c.beta), float(c.alpha), w, dinv, r, p, s, x, u);
+}
+
+// cg_sr_update_stop_k's test on rho = r . r, the sum of the third slab: the criterion of the
+// unpreconditioned form (gamma = r . u is no norm of r). The same bits in every block.
+__global__ __launch_bounds__(kThreads) void pcg_update_stop_k(
+    int64_t n, const double *__restrict__ partialsGamma, const double *__restrict__ partialsDelta, int np,
+    const double *__restrict__ gammaPrev, const double *__restrict__ alphaPrev, const float *w, const float *dinv,
+    float *r, float *p, float *s, float *x, float *u, double *__restrict__ gammaOut, double *__restrict__ alphaOut,
+    double *__restrict__ betaOut, const double *__restrict__ partialsRho, const double *__restrict__ thresh,
+    int *__restrict__ done, int64_t *__restrict__ iters) {
+  __shared__ double sh[kThreads / 64];
+  const SrScalars c = sr_scalars(partialsGamma, partialsDelta, np, gammaPrev, alphaPrev);
+  const double rho = sum_partials<kThreads / 64>(partialsRho, np, sh);
+  if (rho <= *thresh) { // a NaN rho compares false
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+      *gammaOut = c.gamma;
+      *done = 1;
+    }
+    return;
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    *gammaOut = c.gamma;
+    *alphaOut = c.alpha;
+    *betaOut = c.beta;
+    *done = 0;
+    *iters += 1;
+  }
+  pcg_pass(n, float(c.beta), float(c.alpha), w, dinv, r, p, s, x, u);
 }
 
 // The update for NR right-hand sides, interleaved: one pass over the n * NR elements in the quad
@@ -873,6 +1003,50 @@ void check_sr_update(const char *what, bool batched, bool stop, int64_t n, int n
         throw std::runtime_error(pre + "thresh, done, iters and all_done must not alias each other");
 }
 
+// The preconditioned pair's own ground: a launch's vectors and slabs, each read only or written.
+// Nothing a launch writes may share a byte with anything else it touches (two it only reads may)
+struct Access {
+  Span s;
+  bool written;
+};
+
+void check_disjoint(const std::string &pre, std::initializer_list<Access> all) {
+  for (const Access *a = all.begin(); a != all.end(); ++a)
+    for (const Access *b = a + 1; b != all.end(); ++b)
+      if ((a->written || b->written) && overlap(a->s, b->s))
+        throw std::runtime_error(pre + "vectors and slabs must not overlap");
+}
+
+// check_sr_spmv on r and w, then u, the rho slab and the overlaps (`cnt` partials per slab)
+void check_pcg_spmv(const char *what, bool stop, int nRows, int cnt, const int32_t *rowPtr, const int32_t *colInd,
+                    const float *val, const float *r, const float *u, const float *w, const SrState &st) {
+  const std::string pre = std::string(what) + ": ";
+  if (st.k != 1) throw std::runtime_error(pre + "one right-hand side only");
+  check_sr_spmv(what, false, stop, nRows, rowPtr, colInd, val, r, w, st);
+  if (!u || !st.partials_rho) throw std::runtime_error(pre + "null pointer");
+  check_sr_vecs(what, false, {r, u, w});
+  const size_t n = size_t(nRows), c = size_t(cnt);
+  check_disjoint(pre, {{span(r, n), false}, {span(u, n), false}, {span(w, n), true},
+                       {span(st.partials_gamma, c), true}, {span(st.partials_delta, c), true},
+                       {span(st.partials_rho, c), true}});
+}
+
+// check_sr_update on the five vectors, then dinv, u, the rho slab (read with `stop` only) and the overlaps
+void check_pcg_update(const char *what, bool stop, int64_t n, int np, const float *w, const float *dinv,
+                      const float *r, const float *p, const float *s, const float *x, const float *u,
+                      const SrState &st) {
+  const std::string pre = std::string(what) + ": ";
+  if (st.k != 1) throw std::runtime_error(pre + "one right-hand side only");
+  check_sr_update(what, false, stop, n, np, w, r, p, s, x, st);
+  check_sr_vecs(what, false, {dinv, u});
+  if (stop) check_np(what, st.partials_rho, np);
+  const size_t m = size_t(n), c = size_t(np);
+  check_disjoint(pre, {{span(w, m), false}, {span(dinv, m), false}, {span(r, m), true}, {span(p, m), true},
+                       {span(s, m), true}, {span(x, m), true}, {span(u, m), true},
+                       {span(st.partials_gamma, c), false}, {span(st.partials_delta, c), false},
+                       {span(stop ? st.partials_rho : nullptr, c), false}});
+}
+
 // The public signatures say which side of an iteration a launch only reads; SrState serves both
 // launches, so it holds every pointer writable
 SrState sr_state(int k, const double *partialsGamma, const double *partialsDelta, const double *gamma,
@@ -934,8 +1108,43 @@ void sr_update(bool batched, bool stop, int64_t n, int np, const float *w, float
   TZ_HIP_LAUNCH_CHECK();
 }
 
+void sr_pcg_spmv_dot3(bool stop, int nRows, const int32_t *rowPtr, const int32_t *colInd, const float *val,
+                      const float *r, const float *u, float *w, int lanes, const SrState &st, void *stream) {
+  const char *what = stop ? "pcg_spmv_dot3_stop" : "pcg_spmv_dot3";
+  const std::string badLanes = std::string(what) + ": lanes must be kSpmvIlp + 1, 2 or 4";
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  dispatch_ilp(lanes, badLanes.c_str(), [&](auto lanesPerRow, auto depth) {
+    constexpr int W = decltype(lanesPerRow)::value, K = decltype(depth)::value;
+    const int cnt = nRows > 0 ? spmv_dot_partial_count(nRows, W) : 1;
+    check_pcg_spmv(what, stop, nRows, cnt, rowPtr, colInd, val, r, u, w, st);
+    const dim3 g{unsigned(cnt)}, b(kSpmvThreads);
+    auto launch = [&](auto kernel, auto... flag) {
+      hipLaunchKernelGGL(kernel, g, b, 0, s, nRows, rowPtr, colInd, val, r, u, w, st.partials_gamma,
+                         st.partials_delta, st.partials_rho, st.gamma, st.alpha, st.gamma_prev, st.alpha_prev,
+                         flag...);
+    };
+    if (stop) launch(pcg_spmv_dot3_stop_k<W, K>, st.done);
+    else launch(pcg_spmv_dot3_k<W, K>);
+  });
+  TZ_HIP_LAUNCH_CHECK();
+}
 
-// ---- the eight entry points: fill the state, call the launcher
+void sr_pcg_update(bool stop, int64_t n, int np, const float *w, const float *dinv, float *r, float *p, float *s,
+                   float *x, float *u, const SrState &st, void *stream) {
+  const char *what = stop ? "pcg_update_stop" : "pcg_update";
+  hipStream_t stm = static_cast<hipStream_t>(stream);
+  check_pcg_update(what, stop, n, np, w, dinv, r, p, s, x, u, st);
+  const dim3 g(unsigned(dot_partial_count(n))), b(kThreads);
+  auto launch = [&](auto kernel, auto... stopState) {
+    hipLaunchKernelGGL(kernel, g, b, 0, stm, n, st.partials_gamma, st.partials_delta, np, st.gamma_prev,
+                       st.alpha_prev, w, dinv, r, p, s, x, u, st.gamma, st.alpha, st.beta, stopState...);
+  };
+  if (stop) launch(pcg_update_stop_k, static_cast<const double *>(st.partials_rho), st.thresh, st.done, st.iters);
+  else launch(pcg_update_k);
+  TZ_HIP_LAUNCH_CHECK();
+}
+
+// ---- the entry points: fill the state, call the launcher
 
 void csr_spmv_dot2(int nRows, const int32_t *rowPtr, const int32_t *colInd, const float *val, const float *r,
                    float *w, int lanes, double *partialsGamma, double *partialsDelta, const double *gammaOut,
@@ -1000,6 +1209,41 @@ void cg_sr_update_batch_stop(int64_t n, int k, const double *partialsGamma, cons
   SrState st = sr_state(k, partialsGamma, partialsDelta, gammaOut, alphaOut, betaOut, gammaPrev, alphaPrev);
   st.thresh = thresh, st.done = done, st.iters = iters, st.all_done = allDone;
   sr_update(true, true, n, np, W, R, P, S, X, st, stream);
+}
+
+void pcg_spmv_dot3(int nRows, const int32_t *rowPtr, const int32_t *colInd, const float *val, const float *r,
+                   const float *u, float *w, int lanes, double *partialsGamma, double *partialsDelta,
+                   double *partialsRho, const double *gammaOut, const double *alphaOut, double *gammaPrev,
+                   double *alphaPrev, void *stream) {
+  SrState st = sr_state(1, partialsGamma, partialsDelta, gammaOut, alphaOut, nullptr, gammaPrev, alphaPrev);
+  st.partials_rho = partialsRho;
+  sr_pcg_spmv_dot3(false, nRows, rowPtr, colInd, val, r, u, w, lanes, st, stream);
+}
+
+void pcg_spmv_dot3_stop(int nRows, const int32_t *rowPtr, const int32_t *colInd, const float *val, const float *r,
+                        const float *u, float *w, int lanes, double *partialsGamma, double *partialsDelta,
+                        double *partialsRho, const double *gammaOut, const double *alphaOut, double *gammaPrev,
+                        double *alphaPrev, const int *done, void *stream) {
+  SrState st = sr_state(1, partialsGamma, partialsDelta, gammaOut, alphaOut, nullptr, gammaPrev, alphaPrev);
+  st.partials_rho = partialsRho, st.done = const_cast<int *>(done);
+  sr_pcg_spmv_dot3(true, nRows, rowPtr, colInd, val, r, u, w, lanes, st, stream);
+}
+
+void pcg_update(int64_t n, const double *partialsGamma, const double *partialsDelta, int np,
+                const double *gammaPrev, const double *alphaPrev, const float *w, const float *dinv, float *r,
+                float *p, float *s, float *x, float *u, double *gammaOut, double *alphaOut, double *betaOut,
+                void *stream) {
+  const SrState st = sr_state(1, partialsGamma, partialsDelta, gammaOut, alphaOut, betaOut, gammaPrev, alphaPrev);
+  sr_pcg_update(false, n, np, w, dinv, r, p, s, x, u, st, stream);
+}
+
+void pcg_update_stop(int64_t n, const double *partialsGamma, const double *partialsDelta, int np,
+                     const double *gammaPrev, const double *alphaPrev, const float *w, const float *dinv, float *r,
+                     float *p, float *s, float *x, float *u, double *gammaOut, double *alphaOut, double *betaOut,
+                     const double *partialsRho, const double *thresh, int *done, int64_t *iters, void *stream) {
+  SrState st = sr_state(1, partialsGamma, partialsDelta, gammaOut, alphaOut, betaOut, gammaPrev, alphaPrev);
+  st.partials_rho = const_cast<double *>(partialsRho), st.thresh = thresh, st.done = done, st.iters = iters;
+  sr_pcg_update(true, n, np, w, dinv, r, p, s, x, u, st, stream);
 }
 
 } // namespace kern

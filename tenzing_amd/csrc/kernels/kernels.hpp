@@ -360,6 +360,7 @@ struct SrState {
   int *done = nullptr;
   int64_t *iters = nullptr;
   int *all_done = nullptr;
+  double *partials_rho = nullptr; // the preconditioned pair's third slab (r . r); k = 1 only
 };
 /// csr_spmv_dot2 (batched: csr_spmm_dot2 on interleaved r and w), with `stop` its _stop form,
 /// which reads st.done (batched: st.all_done). Every argument is checked here, and an error
@@ -369,6 +370,48 @@ void sr_spmv_dot2(bool batched, bool stop, int nRows, const int32_t *rowPtr, con
 /// cg_sr_update (batched: cg_sr_update_batch), with `stop` its _stop form; likewise
 void sr_update(bool batched, bool stop, int64_t n, int np, const float *w, float *r, float *p, float *s, float *x,
                const SrState &st, void *stream);
+// ---- the same recurrence preconditioned by M = diag(A) (Jacobi), one right-hand side, still two
+// launches. dinv[i] = 1 / a_ii and u = dinv o r are two more f32 vectors; u is stored so that the
+// SpMV gathers one vector, and always holds f32(dinv[i] * r[i]), a rounded product of its own.
+// gamma = r . u and delta = u . (A u) take the places of r . r and r . (A r); beta and alpha are
+// formed from them as cg_sr_update forms them. A third slab, rho = r . r, serves the stopping
+// test, which stays the unpreconditioned form's: rho <= *thresh. No vector or slab of a launch
+// may overlap another unless the launch only reads both; the scalar rules are the parents'.
+/// w = A u as csr_spmv_dot2 computes w = A r (same grid, same mapping, same bits for the same
+/// gathered vector), and block b's shares of r . u, u . w and r . r in the three slabs, b <
+/// spmv_dot_partial_count(nRows, lanes). Block 0 moves the published scalars as csr_spmv_dot2 does.
+void pcg_spmv_dot3(int nRows, const int32_t *rowPtr, const int32_t *colInd, const float *val, const float *r,
+                   const float *u, float *w, int lanes, double *partials_gamma, double *partials_delta,
+                   double *partials_rho, const double *gamma_out, const double *alpha_out, double *gamma_prev,
+                   double *alpha_prev, void *stream);
+/// pcg_spmv_dot3, unless *done is set: then every block returns before it writes anything
+void pcg_spmv_dot3_stop(int nRows, const int32_t *rowPtr, const int32_t *colInd, const float *val, const float *r,
+                        const float *u, float *w, int lanes, double *partials_gamma, double *partials_delta,
+                        double *partials_rho, const double *gamma_out, const double *alpha_out, double *gamma_prev,
+                        double *alpha_prev, const int *done, void *stream);
+/// beta and alpha as cg_sr_update forms them from the two slabs, then with both rounded to f32 and
+/// u_old = f32(dinv * r) (recomputed from the loaded values, not read from u):
+///   p = fmaf(beta, p, u_old), s = fmaf(beta, s, w), x = fmaf(alpha, p, x), r = fmaf(-alpha, s, r),
+///   u = f32(dinv * r)
+/// (same bits as xpay_dev_f32 twice, axpy_dev_f32 twice and one f32 product). Block 0 publishes
+/// gamma, alpha and beta.
+void pcg_update(int64_t n, const double *partials_gamma, const double *partials_delta, int np,
+                const double *gamma_prev, const double *alpha_prev, const float *w, const float *dinv, float *r,
+                float *p, float *s, float *x, float *u, double *gamma_out, double *alpha_out, double *beta_out,
+                void *stream);
+/// pcg_update with the test after its prologue, on rho = the sum of np partials of partials_rho.
+/// rho <= *thresh: no vector, *alpha_out or *beta_out is written; block 0 stores *done = 1 and
+/// gamma. Otherwise pcg_update (same bits), *done = 0 and *iters += 1. A NaN rho never stops.
+void pcg_update_stop(int64_t n, const double *partials_gamma, const double *partials_delta, int np,
+                     const double *gamma_prev, const double *alpha_prev, const float *w, const float *dinv, float *r,
+                     float *p, float *s, float *x, float *u, double *gamma_out, double *alpha_out, double *beta_out,
+                     const double *partials_rho, const double *thresh, int *done, int64_t *iters, void *stream);
+/// The four above as two launchers on an SrState with k = 1 and partials_rho set, as sr_spmv_dot2
+/// and sr_update serve the unpreconditioned eight: every argument is checked here, once
+void sr_pcg_spmv_dot3(bool stop, int nRows, const int32_t *rowPtr, const int32_t *colInd, const float *val,
+                      const float *r, const float *u, float *w, int lanes, const SrState &st, void *stream);
+void sr_pcg_update(bool stop, int64_t n, int np, const float *w, const float *dinv, float *r, float *p, float *s,
+                   float *x, float *u, const SrState &st, void *stream);
 
 /// y += alpha * x (f64)
 void axpy_f64(int64_t n, double alpha, const double *x, double *y, void *stream);

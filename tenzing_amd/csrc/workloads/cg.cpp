@@ -20,7 +20,10 @@
 //          two ops run the batched kernels on interleaved vectors: nrhs independent recurrences,
 //          every slab and scalar an array of nrhs with the same writers. With tol > 0 the two
 //          ops launch the stopping kernels: thresholds <- the host (reset, set_armed), done,
-//          iters and all_done <- block 0 of the update, read by the next spmvdot (dStop_)
+//          iters and all_done <- block 0 of the update, read by the next spmvdot (dStop_).
+//          With precond jacobi the two ops launch the preconditioned pair: the same writers and
+//          readers, and rho slab <- spmvdot, read by the stopping update; u <- the update (and
+//          reset), read by the next spmvdot; dinv <- setup, read by the update
 #include "workloads.hpp"
 
 #include "core/util.hpp"
@@ -48,6 +51,8 @@ Json CgArgs::json() const {
   j["nrhs"] = nrhs;
   j["rhs_first"] = rhs_first;
   j["tol"] = tol;
+  j["precond"] = precond;
+  j["diag_scale"] = diag_scale;
   j["rank"] = rank;
   j["size"] = size;
   return j;
@@ -118,6 +123,13 @@ ConjugateGradient::ConjugateGradient(CgArgs a) : a_(std::move(a)) {
   TZ_CHECK(a_.tol == 0 || a_.form == "sr",
            "CG with tol > 0 needs form sr: only the single-reduction form has kernels that test convergence "
                << "on the device (got tol " << a_.tol << " with form " << a_.form << ")");
+  TZ_CHECK(a_.precond == "none" || a_.precond == "jacobi",
+           "CG precond must be none or jacobi (got " << a_.precond << ")");
+  TZ_CHECK(a_.precond == "none" || (a_.form == "sr" && a_.nrhs == 1),
+           "CG with precond " << a_.precond << " needs form sr and nrhs 1: only the single-reduction form for "
+               << "one right-hand side has preconditioned kernels (got form " << a_.form << " with nrhs "
+               << a_.nrhs << ")");
+  TZ_CHECK(a_.diag_scale >= 0 && a_.diag_scale <= 8, "CG diag_scale must be 0..8 (got " << a_.diag_scale << ")");
   if (!a_.matrix.empty()) {
     A_ = read_matrix_market(a_.matrix);
     TZ_CHECK(A_.rows == A_.cols, a_.matrix << ": CG needs a square matrix, got " << A_.rows << " x " << A_.cols);
@@ -151,6 +163,34 @@ ConjugateGradient::ConjugateGradient(CgArgs a) : a_(std::move(a)) {
       std::mt19937_64 rng((a_.seed ^ 0xC6A4A7935BD1E995ull) + j * 0x9E3779B97F4A7C15ull);
       for (float &v : b_[size_t(c)]) v = float(int64_t(rng() >> 40)) / 8388608.f - 1.f;
     }
+  }
+  // the change of units: powers of two, so every product below is exact
+  scale_.assign(size_t(A_.rows), 1.f);
+  if (a_.diag_scale > 0) {
+    std::mt19937_64 rng(a_.seed ^ 0xD1B54A32D192ED03ull);
+    const uint64_t span = 2 * uint64_t(a_.diag_scale) + 1;
+    for (float &s : scale_) s = std::ldexp(1.f, int(rng() % span) - a_.diag_scale);
+    for (int64_t r = 0; r < A_.rows; ++r)
+      for (int32_t j = A_.rowPtr[size_t(r)]; j < A_.rowPtr[size_t(r + 1)]; ++j)
+        A_.val[size_t(j)] *= scale_[size_t(r)] * scale_[size_t(A_.colInd[size_t(j)])];
+    for (std::vector<float> &bc : b_)
+      for (size_t i = 0; i < bc.size(); ++i) bc[i] *= scale_[i];
+  }
+  if (jacobi()) {
+    dinv_.resize(size_t(A_.rows));
+    for (int64_t r = 0; r < A_.rows; ++r) {
+      const auto b0 = A_.colInd.begin() + A_.rowPtr[size_t(r)], b1 = A_.colInd.begin() + A_.rowPtr[size_t(r + 1)];
+      const auto it = std::find(b0, b1, int32_t(r));
+      TZ_CHECK(it != b1, "CG precond jacobi: row " << r + 1 << " has no diagonal entry");
+      const float d = A_.val[size_t(it - A_.colInd.begin())];
+      TZ_CHECK(std::isfinite(d) && d > 0,
+               "CG precond jacobi: row " << r + 1 << " has the diagonal entry " << d << ", which is not positive "
+                                         << "and finite");
+      dinv_[size_t(r)] = 1.0f / d;
+    }
+    // u = dinv o b, each product rounded to f32 once (a product alone: nothing to contract with)
+    u0_.resize(dinv_.size());
+    for (size_t i = 0; i < u0_.size(); ++i) u0_[i] = dinv_[i] * b_[0][i];
   }
   // the armed thresholds tol^2 * sum_i b[i]^2: the sum in f64 in index order, then one product
   // with tol * tol
@@ -187,7 +227,11 @@ void ConjugateGradient::setup() {
   dQ_ = DeviceBuffer(vb);
   dS_ = DeviceBuffer(vb);
   dW_ = DeviceBuffer(vb);
-  dScal_ = DeviceBuffer((3 * size_t(kern::kCgMaxPartials) + 8) * sizeof(double));
+  dScal_ = DeviceBuffer((4 * size_t(kern::kCgMaxPartials) + 8) * sizeof(double));
+  if (jacobi()) {
+    up(dDinv_, dinv_.data(), dinv_.size() * 4);
+    dU_ = DeviceBuffer(vb);
+  }
   if (a_.nrhs > 1) dBatch_ = DeviceBuffer((2 * size_t(kern::kCgMaxPartials) + 5) * k * sizeof(double));
   if (a_.tol > 0) dStop_ = DeviceBuffer(size_t(a_.nrhs) * 20 + 4);
   dX_ = DeviceBuffer(vb);
@@ -206,6 +250,7 @@ void ConjugateGradient::reset() {
   TZ_HIP(hipMemset(dScal_.get(), 0, dScal_.bytes()));
   TZ_HIP(hipMemcpy(dR_.get(), dB_.get(), vb, hipMemcpyDeviceToDevice));
   TZ_HIP(hipMemcpy(dP_.get(), dB_.get(), vb, hipMemcpyDeviceToDevice));
+  if (jacobi()) dU_.upload(u0_.data(), u0_.size() * 4);
   if (a_.tol > 0) { // iters, done and all_done 0; armed
     TZ_HIP(hipMemset(dStop_.get(), 0, dStop_.bytes()));
     armed_ = true;
@@ -280,6 +325,16 @@ std::vector<float> ConjugateGradient::down(const DeviceBuffer &d, int col) const
   return v;
 }
 
+std::vector<float> ConjugateGradient::u(int col) const {
+  TZ_CHECK(jacobi(), "CG u: this workload was built with precond none and keeps no u");
+  return down(dU_, col);
+}
+
+const std::vector<float> &ConjugateGradient::dinv() const {
+  TZ_CHECK(jacobi(), "CG dinv: this workload was built with precond none");
+  return dinv_;
+}
+
 double ConjugateGradient::rr(int col) const {
   TZ_CHECK(ready(), "CG not set up");
   checked(col);
@@ -319,9 +374,15 @@ double ConjugateGradient::residual(int col) const {
 double ConjugateGradient::check(int k, int col) const {
   const size_t n = size_t(rows());
   const std::vector<float> &bc = this->b(col);
-  std::vector<double> x(n, 0.0), r(bc.begin(), bc.end()), p(r), q(n);
+  // z = M^-1 r with M = diag(A) as the device holds it (dinv), or M = I: rr is r . z throughout
+  const bool pc = jacobi();
+  auto z = [&](size_t i, double ri) { return pc ? double(dinv_[i]) * ri : ri; };
+  std::vector<double> x(n, 0.0), r(bc.begin(), bc.end()), p(n), q(n);
   double rr = 0;
-  for (size_t i = 0; i < n; ++i) rr += r[i] * r[i];
+  for (size_t i = 0; i < n; ++i) {
+    p[i] = z(i, r[i]);
+    rr += r[i] * p[i];
+  }
   for (int it = 0; it < k; ++it) {
     double pq = 0;
     for (size_t i = 0; i < n; ++i) {
@@ -336,11 +397,11 @@ double ConjugateGradient::check(int k, int col) const {
     for (size_t i = 0; i < n; ++i) {
       x[i] += alpha * p[i];
       r[i] -= alpha * q[i];
-      rrNew += r[i] * r[i];
+      rrNew += r[i] * z(i, r[i]);
     }
     const double beta = rr != 0.0 ? rrNew / rr : 0.0;
     rr = rrNew;
-    for (size_t i = 0; i < n; ++i) p[i] = r[i] + beta * p[i];
+    for (size_t i = 0; i < n; ++i) p[i] = z(i, r[i]) + beta * p[i];
   }
   const std::vector<float> xd = this->x(col);
   double err = 0, scale = 0;
@@ -401,7 +462,16 @@ kern::SrState ConjugateGradient::sr_state() const {
     st.gamma_prev = srGammaPrev_(), st.alpha_prev = srAlphaPrev_();
   }
   if (a_.tol > 0) st.thresh = stThresh_(), st.done = stDone_(), st.iters = stIters_(), st.all_done = stAllDone_();
+  if (jacobi()) st.partials_rho = rho_();
   return st;
+}
+void ConjugateGradient::pcg_spmv_dot(void *s) const {
+  kern::sr_pcg_spmv_dot3(a_.tol > 0, int(rows()), dRow_.as<int32_t>(), dCol_.as<int32_t>(), dVal_.as<float>(),
+                         dR_.as<float>(), dU_.as<float>(), dW_.as<float>(), kFusedLanes, sr_state(), s);
+}
+void ConjugateGradient::pcg_update(void *s) const {
+  kern::sr_pcg_update(a_.tol > 0, rows(), np_spmv(), dW_.as<float>(), dDinv_.as<float>(), dR_.as<float>(),
+                      dP_.as<float>(), dS_.as<float>(), dX_.as<float>(), dU_.as<float>(), sr_state(), s);
 }
 void ConjugateGradient::sr_spmv_dot(void *s) const {
   kern::sr_spmv_dot2(a_.nrhs > 1, a_.tol > 0, int(rows()), dRow_.as<int32_t>(), dCol_.as<int32_t>(),
@@ -426,9 +496,18 @@ std::shared_ptr<Graph> ConjugateGradient::sr_graph() const {
                                    8.0 * nnz + 4.0 * nnz * k + 8.0 * n * k, 3.0e6);
   auto up = std::make_shared<CgOp>(self, p + "update", "CgSrUpdate", &ConjugateGradient::sr_update, 3.5,
                                    36.0 * n * k, 4.0e6);
+  if (jacobi()) {
+    // the preconditioned pair, one right-hand side: the SpMV gathers u, reads r and u per row (8
+    // bytes) and writes w; the update reads w, dinv, r, p, s, x and writes p, s, x, r, u (44 bytes
+    // per row: the old u is recomputed, not read)
+    sd = std::make_shared<CgOp>(self, p + "spmvdot", "CgPcgSpmvDot3", &ConjugateGradient::pcg_spmv_dot, 4.5,
+                                12.0 * nnz + 12.0 * n, 3.0e6);
+    up = std::make_shared<CgOp>(self, p + "update", "CgPcgUpdate", &ConjugateGradient::pcg_update, 3.5, 44.0 * n,
+                                4.0e6);
+  }
   auto g = std::make_shared<Graph>();
   g->start_then(sd);
-  g->then(sd, up); // w, both slabs, gamma_prev and alpha_prev
+  g->then(sd, up); // w, the slabs, gamma_prev and alpha_prev
   g->then_finish(up);
   return g;
 }

@@ -893,6 +893,16 @@ struct CgArgs {
   // however many more iterations are launched. 0: the same launches with the same arguments as
   // before this option existed. The recurrence's r is tested, not the true residual.
   double tol = 0.0;
+  // "none", or "jacobi": M = diag(A), the preconditioned single-reduction recurrence in the same
+  // two launches (kern::pcg_spmv_dot3, kern::pcg_update and their _stop forms). Needs form "sr"
+  // and nrhs 1: the batched kernels have no preconditioned form. The stopping test stays
+  // r . r <= tol^2 b . b, so iteration counts compare with "none".
+  std::string precond = "none";
+  // d in 0..8: the same problem in badly chosen units. With e_i uniform in [-d, d] (a generator
+  // seeded with seed ^ 0xD1B54A32D192ED03) and S = diag(2^e_i), the system becomes
+  // (S A S) y = S b: every entry times 2^(e_i + e_j), every b_i times 2^e_i, both exact in f32.
+  // 0 leaves matrix and right-hand sides as they are. Applies to generated and file matrices.
+  int diag_scale = 0;
   std::string prefix = "cg_";
   int rank = 0, size = 1;
   Json json() const;
@@ -913,7 +923,9 @@ public:
   /// x = 0, r = p = b, rr = b . b (and the rr partials that sum to it), s = 0 and the
   /// single-reduction form's scalars 0 (its first iteration then has beta = 0); synchronous.
   /// nrhs > 1: the same per column, b interleaved, every scalar array 0. With tol > 0 also
-  /// iterations = 0, not converged, and the stop armed.
+  /// iterations = 0, not converged, and the stop armed. With precond "jacobi" also
+  /// u = f32(dinv * b); gamma_prev = alpha_prev = 0 as before, so the first iteration has beta = 0
+  /// and alpha = gamma / delta.
   void reset();
   /// tol > 0 only. false: every threshold becomes -1 and the done flags 0; r . r >= 0 never
   /// passes, so the stopping kernels run their full path on every launch, which is what a search
@@ -933,10 +945,17 @@ public:
   std::vector<float> r(int col = 0) const { return down(dR_, col); }
   std::vector<float> p(int col = 0) const { return down(dP_, col); }
   const std::vector<float> &b(int col = 0) const { return b_[size_t(checked(col))]; }
+  /// precond "jacobi" only: the stored u = f32(dinv * r), and dinv[i] = 1.0f / a_ii
+  std::vector<float> u(int col = 0) const;
+  const std::vector<float> &dinv() const;
+  /// the diagonal of S (diag_scale), every entry a power of two; all 1 with diag_scale = 0
+  const std::vector<float> &scale() const { return scale_; }
+  bool jacobi() const { return a_.precond == "jacobi"; }
   /// r . r of the current r (of column `col`) in every form: its partials as dot_partials_f32
   /// writes them (the bits of the plain and fused forms' rr slab), summed in the kernels' order
   double rr(int col = 0) const;
-  /// max |x - x_ref| / max |x_ref| against k iterations of CG in f64 on the host (same guards)
+  /// max |x - x_ref| / max |x_ref| against k iterations of CG in f64 on the host (same guards);
+  /// with precond "jacobi" against k iterations of CG preconditioned by the same dinv
   double check(int k, int col = 0) const;
   /// the true residual ||b - A x||_2 / ||b||_2 of the current x, in f64 on the host (0 for b = 0).
   /// The single-reduction form's r is a recurrence of its own, so rr() no longer is this quantity
@@ -962,6 +981,8 @@ public:
   void fused_p(void *stream) const;
   void sr_spmv_dot(void *stream) const; // w = A r, gamma and delta partials; the scalars move on
   void sr_update(void *stream) const;   // beta, alpha; p, s, x, r
+  void pcg_spmv_dot(void *stream) const; // w = A u, gamma, delta and rho partials; the scalars move on
+  void pcg_update(void *stream) const;   // beta, alpha; p, s, x, r, u
 
 private:
   std::vector<float> down(const DeviceBuffer &d, int col) const;
@@ -974,9 +995,13 @@ private:
   std::vector<std::vector<float>> b_; // one per column
   DeviceBuffer dRow_, dCol_, dVal_, dB_, dX_, dR_, dP_, dQ_;
   DeviceBuffer dS_, dW_; // the single-reduction form: s = A p by recurrence, w = A r
+  DeviceBuffer dDinv_, dU_; // precond "jacobi": 1 / a_ii, and u = dinv o r (then w = A u)
+  std::vector<float> dinv_, u0_; // u0 = f32(dinv * b), the start state's u
+  std::vector<float> scale_;
   // [pq partials 256 | rr partials 256 | rr | alpha | beta | the single-reduction form's gamma,
-  //  alpha, beta, gamma_prev, alpha_prev | rr()'s scratch partials 256]; that form's delta slab
-  // is the pq slab and its gamma slab the rr slab
+  //  alpha, beta, gamma_prev, alpha_prev | rr()'s scratch partials 256 | rho partials 256]; that
+  // form's delta slab is the pq slab and its gamma slab the rr slab; the rho slab (r . r beside a
+  // gamma that is r . u) serves precond "jacobi" only
   DeviceBuffer dScal_;
   double *pq_() const { return dScal_.as<double>(); }
   double *rrp_() const { return dScal_.as<double>() + kern::kCgMaxPartials; }
@@ -989,6 +1014,7 @@ private:
   double *srGammaPrev_() const { return rr_() + 6; }
   double *srAlphaPrev_() const { return rr_() + 7; }
   double *scratch_() const { return rr_() + 8; }
+  double *rho_() const { return scratch_() + kern::kCgMaxPartials; }
   // nrhs > 1: [delta slabs nrhs x 256 | gamma slabs nrhs x 256 | gamma, alpha, beta, gamma_prev,
   //  alpha_prev: nrhs each]; dScal_ then only serves rr()
   DeviceBuffer dBatch_;

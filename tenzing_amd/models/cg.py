@@ -10,7 +10,8 @@ r.r and r.(A r), then one update of p, s, x and r; ``form="all"`` offers all thr
 With ``nrhs`` = 2, 4 or 8 the single-reduction form solves that many right-hand sides in the same
 two launches: one matrix stream and one gather per entry serve every column. With ``tol`` > 0
 that form stops each column on the device at r.r <= tol^2 b.b and freezes it; ``solve`` drives a
-prepared runtime until every column has stopped.
+prepared runtime until every column has stopped. ``precond="jacobi"`` runs that form preconditioned
+by diag(A), still in two launches; ``diag_scale`` poses the same problem in badly chosen units.
 """
 from __future__ import annotations
 
@@ -41,6 +42,13 @@ class CgConfig:
     # stays frozen however many more iterations are launched; iterations(j), converged(j) and
     # threshold(j) report, set_armed(False) switches the test off for timing loops. 0: no test
     tol: float = 0.0
+    # none | jacobi: M = diag(A), the preconditioned single-reduction recurrence in the same two
+    # launches (form="sr" and nrhs=1 only). The stopping test stays r.r <= tol^2 b.b; u() and dinv()
+    # read the stored u = f32(dinv * r) and dinv = 1 / a_ii
+    precond: str = "none"
+    # d in 0..8: the same problem in badly chosen units, (S A S) y = S b with S = diag(2^e_i), e_i
+    # uniform in [-d, d] from seed; exact in f32. scale() returns S's diagonal. 0: as generated / read
+    diag_scale: int = 0
     prefix: str = "cg_"
 
     def args(self, rank: int = 0, size: int = 1, device: int = -1) -> "_tz.CgArgs":
@@ -48,6 +56,7 @@ class CgConfig:
         a.m, a.bw, a.nnz, a.seed = self.m, self.bw, self.nnz, self.seed
         a.matrix, a.form, a.lanes, a.rhs, a.prefix = self.matrix, self.form, self.lanes, self.rhs, self.prefix
         a.nrhs, a.rhs_first, a.tol = self.nrhs, self.rhs_first, self.tol
+        a.precond, a.diag_scale = self.precond, self.diag_scale
         a.rank, a.size, a.device = rank, size, device
         return a
 
