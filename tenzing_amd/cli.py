@@ -60,7 +60,8 @@ def _build_workload(a, ctrl, device, setup):
         return g, {"halo": h, "spmv": s}
     if a.workload == "cg":
         c, g = build_cg(CgConfig(m=a.cg_m, form=a.cg_form, matrix=a.cg_matrix, nrhs=a.cg_nrhs,
-                                 tol=a.cg_tol, precond=a.cg_precond, diag_scale=a.cg_diag_scale),
+                                 tol=a.cg_tol, precond=a.cg_precond, diag_scale=a.cg_diag_scale,
+                                 refine_tol=a.cg_refine_tol),
                         ctrl, device, setup)
         return g, {"cg": c}
     if a.workload == "noop":
@@ -225,7 +226,7 @@ _WORKLOAD_KEYS = ("workload", "noop_width", "streams", "halo_n", "nq", "ghost", 
                   "stencil", "rank_grid",
                   "spmv_m", "spmv_matrix", "spmv_form", "spmv_transport", "spmv_library",
                   "spmv_distribute", "cg_m", "cg_form", "cg_matrix", "cg_nrhs", "cg_tol",
-                  "cg_max_iters", "cg_check_iters", "cg_precond", "cg_diag_scale",
+                  "cg_max_iters", "cg_check_iters", "cg_precond", "cg_diag_scale", "cg_refine_tol",
                   "cu_partition", "stream_priorities")
 
 
@@ -358,7 +359,15 @@ def cmd_run(a) -> int:
             out["cg_iterations"] = max(sol.iterations)
             out["cg_converged"] = all(sol.converged)
             out["cg_residual"] = max(sol.residual)
-            ok &= out["cg_converged"]
+            if w.cg_refine_tol > 0:
+                # the refined solve: cg_converged and cg_residual describe its last inner solve
+                out["cg_refine_tol"] = w.cg_refine_tol
+                out["cg_outer_steps"] = sol.outer_steps
+                out["cg_refined"] = sol.refined
+                out["cg_residual64"] = sol.residual64
+                ok &= sol.refined
+            else:
+                ok &= out["cg_converged"]
             wl["cg"].reset()
             wl["cg"].set_armed(False)  # warm up and time full iterations
     rt.precompile(a.warmup)
@@ -581,6 +590,11 @@ def _parser() -> argparse.ArgumentParser:
     s.add_argument("--cg-diag-scale", type=int, default=0,
                    help="cg: pose the same problem in badly chosen units, (S A S) y = S b with "
                         "S = diag(2^e), e uniform in [-N, N] (0..8; 0: the matrix as it is)")
+    s.add_argument("--cg-refine-tol", type=float, default=0.0,
+                   help="cg (needs --cg-form sr, --cg-nrhs 1 and 0 < this < --cg-tol): f64 iterative "
+                        "refinement around the f32 solve, until ||b - A x64|| <= this * ||b|| in f64; "
+                        "--cg-tol is then the inner solve's relative tolerance. `run` reports "
+                        "cg_outer_steps, cg_refined and cg_residual64. 0: off")
     s.add_argument("--cg-max-iters", type=int, default=1000,
                    help="cg with --cg-tol, `run`: iterations the solve may launch")
     s.add_argument("--cg-check-iters", type=int, default=25,

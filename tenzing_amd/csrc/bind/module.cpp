@@ -1198,12 +1198,14 @@ PYBIND11_MODULE(_tz, m) {
       .def_readwrite("tol", &CgArgs::tol)
       .def_readwrite("precond", &CgArgs::precond)
       .def_readwrite("diag_scale", &CgArgs::diag_scale)
+      .def_readwrite("refine_tol", &CgArgs::refine_tol)
       .def_readwrite("prefix", &CgArgs::prefix)
       .def_readwrite("rank", &CgArgs::rank)
       .def_readwrite("size", &CgArgs::size)
       .def("json", [](const CgArgs &a) { return a.json().dump(); });
   {
     auto f32 = [](const std::vector<float> &v) { return py::array_t<float>(py::ssize_t(v.size()), v.data()); };
+    auto f64 = [](const std::vector<double> &v) { return py::array_t<double>(py::ssize_t(v.size()), v.data()); };
     py::class_<ConjugateGradient, std::shared_ptr<ConjugateGradient>>(m, "ConjugateGradient")
         .def(py::init([](const CgArgs &a) { return std::make_shared<ConjugateGradient>(a); }), py::arg("args"))
         .def_property_readonly("args", &ConjugateGradient::args)
@@ -1221,6 +1223,8 @@ PYBIND11_MODULE(_tz, m) {
              "column col (0 .. nrhs - 1) of x, de-interleaved; likewise r, p, b, rr, check and residual")
         .def("r", [f32](const ConjugateGradient &c, int col) { return f32(c.r(col)); }, py::arg("col") = 0)
         .def("p", [f32](const ConjugateGradient &c, int col) { return f32(c.p(col)); }, py::arg("col") = 0)
+        .def("s", [f32](const ConjugateGradient &c, int col) { return f32(c.s(col)); }, py::arg("col") = 0,
+             "the single-reduction form's s = A p by recurrence")
         .def("b", [f32](const ConjugateGradient &c, int col) { return f32(c.b(col)); }, py::arg("col") = 0)
         .def("u", [f32](const ConjugateGradient &c, int col) { return f32(c.u(col)); }, py::arg("col") = 0,
              "precond jacobi: the stored u = f32(dinv * r)")
@@ -1246,7 +1250,24 @@ PYBIND11_MODULE(_tz, m) {
         .def("converged", &ConjugateGradient::converged, py::arg("col") = 0,
              "tol > 0: whether column col's last update found r . r <= threshold (synchronous)")
         .def("threshold", &ConjugateGradient::threshold, py::arg("col") = 0,
-             "tol > 0: the armed threshold tol^2 * sum b[i]^2 of column col");
+             "tol > 0: the armed threshold tol^2 * sum b[i]^2 of column col")
+        .def("refine_step", &ConjugateGradient::refine_step, py::call_guard<py::gil_scoped_release>(),
+             "refine_tol > 0: x64 += x, x = 0; r64 = b - A x64 in f64 on the device; refined, or the f32 "
+             "recurrence restarts on f32(r64) with the inner threshold tol^2 r . r (synchronous)")
+        .def("x64", [f64](const ConjugateGradient &c) { return f64(c.x64()); },
+             "refine_tol > 0: the f64 solution")
+        .def("r64", [f64](const ConjugateGradient &c) { return f64(c.r64()); },
+             "refine_tol > 0: b - A x64 as the last refinement step formed it, in f64")
+        .def("outer_steps", &ConjugateGradient::outer_steps,
+             "refine_tol > 0: restarts of the inner solve since reset()")
+        .def("refined", &ConjugateGradient::refined,
+             "refine_tol > 0: whether a step found r64 . r64 <= refine_tol^2 b . b")
+        .def("inner_threshold", &ConjugateGradient::inner_threshold,
+             "refine_tol > 0: the threshold the inner solve tests now (the device's value)")
+        .def("rr64", &ConjugateGradient::rr64, "refine_tol > 0: r64 . r64 as the last step summed it")
+        .def("outer_threshold", &ConjugateGradient::outer_threshold, "refine_tol > 0: refine_tol^2 * sum b[i]^2")
+        .def("residual64", &ConjugateGradient::residual64, py::call_guard<py::gil_scoped_release>(),
+             "refine_tol > 0: ||b - A x64|| / ||b|| in f64 on the host");
   }
   m.def("read_matrix_market", [](const std::string &path) {
     CsrHost a = read_matrix_market(path);
@@ -1510,6 +1531,31 @@ PYBIND11_MODULE(_tz, m) {
      py::arg("alpha_prev"), py::arg("w"), py::arg("dinv"), py::arg("r"), py::arg("p"), py::arg("s"), py::arg("x"),
      py::arg("u"), py::arg("gamma_out"), py::arg("alpha_out"), py::arg("beta_out"), py::arg("partials_rho"),
      py::arg("thresh"), py::arg("done"), py::arg("iters"), py::arg("stream") = 0);
+  k.def("cg_refine_accumulate", [](int64_t n, uintptr_t x, uintptr_t sv, uintptr_t x64, uintptr_t outerDone,
+                                   uintptr_t s) {
+    kern::cg_refine_accumulate(n, as<float>(x), as<float>(sv), as<double>(x64), as<const int>(outerDone), P(s));
+  }, py::arg("n"), py::arg("x"), py::arg("s"), py::arg("x64"), py::arg("outer_done"), py::arg("stream") = 0);
+  k.def("cg_refine_partial_count", &kern::cg_refine_partial_count, py::arg("n_rows"));
+  k.def("cg_refine_residual", [](int n, uintptr_t rp, uintptr_t ci, uintptr_t v, uintptr_t b, uintptr_t x64,
+                                 uintptr_t dinv, uintptr_t r64, uintptr_t r, uintptr_t p, uintptr_t u, uintptr_t p64,
+                                 uintptr_t p32, uintptr_t outerDone, uintptr_t s) {
+    kern::cg_refine_residual(n, as<ci32>(rp), as<ci32>(ci), as<cf>(v), as<cf>(b), as<cd>(x64), as<cf>(dinv),
+                             as<double>(r64), as<float>(r), as<float>(p), as<float>(u), as<double>(p64),
+                             as<double>(p32), as<const int>(outerDone), P(s));
+  }, py::arg("n_rows"), py::arg("row_ptr"), py::arg("col_ind"), py::arg("val"), py::arg("b"), py::arg("x64"),
+     py::arg("dinv"), py::arg("r64"), py::arg("r"), py::arg("p"), py::arg("u"), py::arg("partials64"),
+     py::arg("partials32"), py::arg("outer_done"), py::arg("stream") = 0);
+  k.def("cg_refine_decide", [](uintptr_t p64, uintptr_t p32, int np, double tol2, uintptr_t thresh, uintptr_t done,
+                               uintptr_t g, uintptr_t a, uintptr_t b, uintptr_t gPrev, uintptr_t aPrev,
+                               uintptr_t oThresh, uintptr_t oDone, uintptr_t oSteps, uintptr_t oRr, uintptr_t s) {
+    kern::RefineOuter o;
+    o.thresh = as<cd>(oThresh), o.done = as<int>(oDone), o.steps = as<int64_t>(oSteps), o.rr64 = as<double>(oRr);
+    kern::cg_refine_decide(as<cd>(p64), as<cd>(p32), np, tol2, as<double>(thresh), as<int>(done), as<double>(g),
+                           as<double>(a), as<double>(b), as<double>(gPrev), as<double>(aPrev), o, P(s));
+  }, py::arg("partials64"), py::arg("partials32"), py::arg("np"), py::arg("tol2"), py::arg("thresh"),
+     py::arg("done"), py::arg("gamma"), py::arg("alpha"), py::arg("beta"), py::arg("gamma_prev"),
+     py::arg("alpha_prev"), py::arg("outer_thresh"), py::arg("outer_done"), py::arg("outer_steps"),
+     py::arg("outer_rr64"), py::arg("stream") = 0);
   k.def("csr_spmm_dot2_stop", [](int n, uintptr_t rp, uintptr_t ci, uintptr_t v, uintptr_t r, uintptr_t w,
                                  int nrhs, int lanes, uintptr_t pg, uintptr_t pd, uintptr_t gOut, uintptr_t aOut,
                                  uintptr_t gPrev, uintptr_t aPrev, uintptr_t allDone, uintptr_t s) {

@@ -412,6 +412,41 @@ void sr_pcg_spmv_dot3(bool stop, int nRows, const int32_t *rowPtr, const int32_t
                       const float *r, const float *u, float *w, int lanes, const SrState &st, void *stream);
 void sr_pcg_update(bool stop, int64_t n, int np, const float *w, const float *dinv, float *r, float *p, float *s,
                    float *x, float *u, const SrState &st, void *stream);
+// ---- mixed-precision iterative refinement around that f32 solve (cg_refine_kernels.hip): the
+// solution is kept in f64, the residual b - A x64 is evaluated in f64 (A and b are f32 data, exact
+// in f64), and the f32 recurrence solves A d = r64 to a modest tolerance again and again. One
+// refinement step is the three launches below, in this order on one stream. The outer state
+// (RefineOuter) must not share a byte with the iteration's scalars or the stop state, or with
+// itself: the rule of thresh, done and iters above. Every launch returns before it writes
+// anything once *outer.done is set, decided uniformly over its grid as *done is read above.
+/// the outer threshold refine_tol^2 * b . b (the host's), the refined flag, the restarts of the
+/// inner solve so far, and the last r64 . r64
+struct RefineOuter {
+  const double *thresh = nullptr;
+  int *done = nullptr;
+  int64_t *steps = nullptr;
+  double *rr64 = nullptr;
+};
+/// x64[i] += double(x[i]) (one f64 add), then x[i] = s[i] = 0. f32 vectors 4-byte aligned.
+void cg_refine_accumulate(int64_t n, float *x, float *s, double *x64, const int *outer_done, void *stream);
+/// partials the next launch writes per slab: spmv_dot_partial_count(nRows, 4)
+int cg_refine_partial_count(int nRows);
+/// r64[i] = double(b[i]) - sum_j double(a_ij) * x64[col_j], products and sums in f64 (4 lanes per
+/// row, a fixed order: the same bits on every call), and r[i] = p[i] = f32(r64[i]). With dinv and u
+/// (both or neither): u[i] = f32(dinv[i] * r[i]), a rounded product of its own as pcg_update keeps
+/// it, and p[i] = u[i]. partials64[b] = block b's share of r64 . r64, partials32[b] of r . r (the
+/// new f32 vector), b < cg_refine_partial_count(nRows).
+void cg_refine_residual(int nRows, const int32_t *rowPtr, const int32_t *colInd, const float *val, const float *b,
+                        const double *x64, const float *dinv, double *r64, float *r, float *p, float *u,
+                        double *partials64, double *partials32, const int *outer_done, void *stream);
+/// One block. With rr64 and rr32 the sums of np partials of the two slabs (sum_partials_f64's
+/// order), *outer.rr64 = rr64. rr64 <= *outer.thresh (a NaN never passes): *outer.done = 1 and
+/// nothing else is written. Otherwise the inner solve restarts: *thresh = tol2 * rr32, *done = 0,
+/// the five scalars +0.0 (the next update then has beta = 0) and *outer.steps += 1. The inner
+/// solve's iters is not an argument: it counts over the whole solve.
+void cg_refine_decide(const double *partials64, const double *partials32, int np, double tol2, double *thresh,
+                      int *done, double *gamma, double *alpha, double *beta, double *gamma_prev, double *alpha_prev,
+                      const RefineOuter &outer, void *stream);
 
 /// y += alpha * x (f64)
 void axpy_f64(int64_t n, double alpha, const double *x, double *y, void *stream);

@@ -24,6 +24,10 @@
 //          With precond jacobi the two ops launch the preconditioned pair: the same writers and
 //          readers, and rho slab <- spmvdot, read by the stopping update; u <- the update (and
 //          reset), read by the next spmvdot; dinv <- setup, read by the update
+//          With refine_tol > 0 the same two ops with the same arguments. refine_step() is no op
+//          of the graph: between two device synchronizes, on the null stream, it writes x64, r64,
+//          its two slabs and the outer state (dRefine_, a buffer of its own), and x, s, r, p (u),
+//          the inner threshold, done and the five scalars, as reset() writes them
 #include "workloads.hpp"
 
 #include "core/util.hpp"
@@ -53,6 +57,7 @@ Json CgArgs::json() const {
   j["tol"] = tol;
   j["precond"] = precond;
   j["diag_scale"] = diag_scale;
+  j["refine_tol"] = refine_tol;
   j["rank"] = rank;
   j["size"] = size;
   return j;
@@ -120,6 +125,20 @@ ConjugateGradient::ConjugateGradient(CgArgs a) : a_(std::move(a)) {
                << a_.nrhs << " with form " << a_.form << ")");
   TZ_CHECK(a_.rhs_first >= 0, "CG rhs_first must not be negative (got " << a_.rhs_first << ")");
   TZ_CHECK(std::isfinite(a_.tol) && a_.tol >= 0, "CG tol must be finite and not negative (got " << a_.tol << ")");
+  TZ_CHECK(std::isfinite(a_.refine_tol) && a_.refine_tol >= 0,
+           "CG refine_tol must be finite and not negative (got " << a_.refine_tol << ")");
+  if (a_.refine_tol > 0) {
+    TZ_CHECK(a_.form == "sr", "CG with refine_tol > 0 needs form sr: the refinement step restarts the "
+                                  << "single-reduction recurrence (got refine_tol " << a_.refine_tol << " with form "
+                                  << a_.form << ")");
+    TZ_CHECK(a_.nrhs == 1, "CG with refine_tol > 0 needs nrhs 1: batched refinement is not built (got nrhs "
+                               << a_.nrhs << ")");
+    TZ_CHECK(a_.tol > 0, "CG with refine_tol > 0 needs tol > 0: tol is the inner solve's relative tolerance, "
+                             << "and without it the f32 solve never stops (got tol 0)");
+    TZ_CHECK(a_.refine_tol < a_.tol, "CG refine_tol must be below tol: the inner f32 solve to tol already reaches "
+                                         << "tol, refinement is for what lies beyond it (got refine_tol "
+                                         << a_.refine_tol << " with tol " << a_.tol << ")");
+  }
   TZ_CHECK(a_.tol == 0 || a_.form == "sr",
            "CG with tol > 0 needs form sr: only the single-reduction form has kernels that test convergence "
                << "on the device (got tol " << a_.tol << " with form " << a_.form << ")");
@@ -198,6 +217,7 @@ ConjugateGradient::ConjugateGradient(CgArgs a) : a_(std::move(a)) {
     double bb = 0;
     for (float v : b_[size_t(c)]) bb += double(v) * double(v);
     thresh_.push_back(a_.tol * a_.tol * bb);
+    if (refining()) outerThresh_ = a_.refine_tol * a_.refine_tol * bb; // nrhs = 1: the same b . b
   }
   const int W = a_.lanes - kern::kSpmvIlp;
   TZ_CHECK(a_.lanes == -1 || a_.lanes == 0 || W == 1 || W == 2 || W == 4 ||
@@ -234,6 +254,11 @@ void ConjugateGradient::setup() {
   }
   if (a_.nrhs > 1) dBatch_ = DeviceBuffer((2 * size_t(kern::kCgMaxPartials) + 5) * k * sizeof(double));
   if (a_.tol > 0) dStop_ = DeviceBuffer(size_t(a_.nrhs) * 20 + 4);
+  if (refining()) {
+    dX64_ = DeviceBuffer(std::max<size_t>(size_t(rows()) * sizeof(double), 16));
+    dR64_ = DeviceBuffer(dX64_.bytes());
+    dRefine_ = DeviceBuffer((2 * size_t(kern::kCgMaxPartials) + 4) * sizeof(double));
+  }
   dX_ = DeviceBuffer(vb);
   reset();
 }
@@ -256,6 +281,13 @@ void ConjugateGradient::reset() {
     armed_ = true;
     upload_thresholds();
   }
+  if (refining()) { // x64 = r64 = 0, both slabs, the step count and the flag 0; the outer threshold
+    TZ_HIP(hipMemset(dX64_.get(), 0, dX64_.bytes()));
+    TZ_HIP(hipMemset(dR64_.get(), 0, dR64_.bytes()));
+    TZ_HIP(hipMemset(dRefine_.get(), 0, dRefine_.bytes()));
+    TZ_HIP(hipMemcpy(rfThresh_(), &outerThresh_, sizeof(double), hipMemcpyHostToDevice));
+    stepped_ = false;
+  }
   if (a_.nrhs > 1) { // the batched form keeps no rr: every scalar array starts at 0
     TZ_HIP(hipMemset(dBatch_.get(), 0, dBatch_.bytes()));
     TZ_HIP(hipDeviceSynchronize());
@@ -275,6 +307,8 @@ void ConjugateGradient::upload_thresholds() const {
 void ConjugateGradient::set_armed(bool armed) {
   TZ_CHECK(ready(), "CG not set up");
   TZ_CHECK(a_.tol > 0, "CG set_armed: this workload was built with tol = 0 and has no stopping test");
+  TZ_CHECK(!stepped_, "CG set_armed: a refinement step was taken since the last reset(), and the inner threshold "
+                          << "is the device's now; reset() first");
   TZ_HIP(hipDeviceSynchronize());
   armed_ = armed;
   upload_thresholds();
@@ -306,6 +340,99 @@ double ConjugateGradient::threshold(int col) const {
   TZ_CHECK(a_.tol > 0, "CG threshold: this workload was built with tol = 0");
   if (ready()) TZ_HIP(hipDeviceSynchronize());
   return thresh_[size_t(checked(col))];
+}
+
+// ------------------------------------------------------------------ iterative refinement
+
+void ConjugateGradient::check_refining(const char *what) const {
+  TZ_CHECK(refining(), "CG " << what << ": this workload was built with refine_tol = 0 and keeps no f64 state");
+  TZ_CHECK(ready(), "CG not set up");
+}
+
+void ConjugateGradient::refine_step() {
+  check_refining("refine_step");
+  TZ_CHECK(armed_, "CG refine_step: the workload is disarmed (set_armed(false)); a step restarts the inner solve "
+                       << "with a threshold of its own, so reset() first");
+  // synchronous like reset(): schedules run on non-blocking streams that the null stream does not order with
+  TZ_HIP(hipDeviceSynchronize());
+  stepped_ = true;
+  const kern::SrState st = sr_state();
+  kern::cg_refine_accumulate(rows(), dX_.as<float>(), dS_.as<float>(), dX64_.as<double>(), rfDone_(), nullptr);
+  kern::cg_refine_residual(int(rows()), dRow_.as<int32_t>(), dCol_.as<int32_t>(), dVal_.as<float>(),
+                           dB_.as<float>(), dX64_.as<double>(), jacobi() ? dDinv_.as<float>() : nullptr,
+                           dR64_.as<double>(), dR_.as<float>(), dP_.as<float>(),
+                           jacobi() ? dU_.as<float>() : nullptr, rfP64_(), rfP32_(), rfDone_(), nullptr);
+  kern::RefineOuter o;
+  o.thresh = rfThresh_(), o.done = rfDone_(), o.steps = rfSteps_(), o.rr64 = rfRr64_();
+  kern::cg_refine_decide(rfP64_(), rfP32_(), kern::cg_refine_partial_count(int(rows())), a_.tol * a_.tol,
+                         stThresh_(), st.done, st.gamma, st.alpha, st.beta, st.gamma_prev, st.alpha_prev, o, nullptr);
+  TZ_HIP(hipDeviceSynchronize());
+}
+
+std::vector<double> ConjugateGradient::down64(const DeviceBuffer &d) const {
+  TZ_HIP(hipDeviceSynchronize());
+  std::vector<double> v(static_cast<size_t>(rows()));
+  d.download(v.data(), v.size() * sizeof(double));
+  return v;
+}
+
+std::vector<double> ConjugateGradient::x64() const {
+  check_refining("x64");
+  return down64(dX64_);
+}
+
+std::vector<double> ConjugateGradient::r64() const {
+  check_refining("r64");
+  return down64(dR64_);
+}
+
+namespace {
+template <typename T> T peek(const T *dev) {
+  TZ_HIP(hipDeviceSynchronize());
+  T v{};
+  TZ_HIP(hipMemcpy(&v, dev, sizeof v, hipMemcpyDeviceToHost));
+  return v;
+}
+} // namespace
+
+int64_t ConjugateGradient::outer_steps() const {
+  check_refining("outer_steps");
+  return peek(rfSteps_());
+}
+
+bool ConjugateGradient::refined() const {
+  check_refining("refined");
+  return peek(rfDone_()) != 0;
+}
+
+double ConjugateGradient::inner_threshold() const {
+  check_refining("inner_threshold");
+  return peek(stThresh_());
+}
+
+double ConjugateGradient::rr64() const {
+  check_refining("rr64");
+  return peek(rfRr64_());
+}
+
+double ConjugateGradient::outer_threshold() const {
+  TZ_CHECK(refining(), "CG outer_threshold: this workload was built with refine_tol = 0");
+  return outerThresh_;
+}
+
+double ConjugateGradient::residual64() const {
+  const std::vector<double> xd = this->x64();
+  const std::vector<float> &bc = this->b(0);
+  double res = 0, bb = 0;
+  for (size_t i = 0; i < size_t(rows()); ++i) {
+    double s = 0;
+    for (int32_t j = A_.rowPtr[i]; j < A_.rowPtr[i + 1]; ++j)
+      s += double(A_.val[size_t(j)]) * xd[size_t(A_.colInd[size_t(j)])];
+    const double d = double(bc[i]) - s;
+    res += d * d;
+    bb += double(bc[i]) * double(bc[i]);
+  }
+  return bb > 0 ? std::sqrt(res / bb) : std::sqrt(res);
 }
 
 int ConjugateGradient::checked(int col) const {

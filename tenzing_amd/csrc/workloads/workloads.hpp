@@ -903,6 +903,13 @@ struct CgArgs {
   // (S A S) y = S b: every entry times 2^(e_i + e_j), every b_i times 2^e_i, both exact in f32.
   // 0 leaves matrix and right-hand sides as they are. Applies to generated and file matrices.
   int diag_scale = 0;
+  // > 0 (form "sr", nrhs 1, tol > 0 and refine_tol < tol): mixed-precision iterative refinement.
+  // The workload also keeps x64 and r64 (f64); refine_step() adds the f32 solve's x to x64, forms
+  // r64 = b - A x64 in f64 on the device and restarts the f32 recurrence on f32(r64) with x = 0
+  // and the inner threshold tol^2 r . r, until r64 . r64 <= refine_tol^2 b . b. tol is then the
+  // inner solve's relative tolerance. The iteration's two launches and their arguments are the
+  // ones of refine_tol = 0; the step is not part of the searched schedule.
+  double refine_tol = 0.0;
   std::string prefix = "cg_";
   int rank = 0, size = 1;
   Json json() const;
@@ -925,13 +932,15 @@ public:
   /// nrhs > 1: the same per column, b interleaved, every scalar array 0. With tol > 0 also
   /// iterations = 0, not converged, and the stop armed. With precond "jacobi" also
   /// u = f32(dinv * b); gamma_prev = alpha_prev = 0 as before, so the first iteration has beta = 0
-  /// and alpha = gamma / delta.
+  /// and alpha = gamma / delta. With refine_tol > 0 also x64 = r64 = 0, no outer step taken, not
+  /// refined.
   void reset();
   /// tol > 0 only. false: every threshold becomes -1 and the done flags 0; r . r >= 0 never
   /// passes, so the stopping kernels run their full path on every launch, which is what a search
   /// or a timing loop that replays thousands of iterations on one state must measure. true:
   /// thresholds back to tol^2 b . b. The state after setup() and reset() is armed. Meant to be
   /// switched on a fresh state (reset() first): a recurrence that has stopped does not resume.
+  /// Throws once refine_step() has run since the last reset(): the device owns the threshold then.
   void set_armed(bool armed);
   bool armed() const { return armed_; }
   /// tol > 0 only, all synchronous: iterations column `col` took before it stopped (or so far),
@@ -940,10 +949,35 @@ public:
   bool converged(int col = 0) const;
   /// and its armed threshold tol^2 * sum_i b[i]^2 (f64, index order), whatever set_armed says
   double threshold(int col = 0) const;
+  /// refine_tol > 0 only; synchronous like reset() (device synchronize, at most three launches on
+  /// the null stream, synchronize), all arithmetic on the device (kern::cg_refine_*):
+  ///   x64 += x, x = s = 0; r64 = b - A x64 in f64, r = p = f32(r64) (jacobi: u = f32(dinv * r),
+  ///   p = u); then r64 . r64 <= refine_tol^2 b . b: refined, and nothing more is written; else the
+  ///   inner threshold becomes tol^2 r . r, done 0, the five scalars 0 and outer_steps goes up.
+  /// Valid at any time, not only once the inner solve has stopped; on a refined state it writes
+  /// nothing (decided on the device). Throws on a disarmed workload; iterations() keeps counting
+  /// inner iterations over the whole solve.
+  void refine_step();
+  /// refine_tol > 0 only, all synchronous: the f64 solution and the last f64 residual b - A x64,
+  std::vector<double> x64() const;
+  std::vector<double> r64() const;
+  /// restarts of the inner solve since reset() (a step that finds the solve refined adds none),
+  int64_t outer_steps() const;
+  /// whether a step found r64 . r64 <= refine_tol^2 b . b,
+  bool refined() const;
+  /// the threshold the inner solve tests now (the device's value; threshold() stays tol^2 b . b),
+  double inner_threshold() const;
+  /// r64 . r64 as the last step summed it (0 before the first), and the outer threshold
+  double rr64() const;
+  double outer_threshold() const;
+  /// ||b - A x64||_2 / ||b||_2 in f64 on the host: residual()'s counterpart for x64
+  double residual64() const;
   /// column `col` (0 .. nrhs - 1) of the state, de-interleaved; anything else throws
   std::vector<float> x(int col = 0) const { return down(dX_, col); }
   std::vector<float> r(int col = 0) const { return down(dR_, col); }
   std::vector<float> p(int col = 0) const { return down(dP_, col); }
+  /// the single-reduction form's s = A p by recurrence (0 in the other forms)
+  std::vector<float> s(int col = 0) const { return down(dS_, col); }
   const std::vector<float> &b(int col = 0) const { return b_[size_t(checked(col))]; }
   /// precond "jacobi" only: the stored u = f32(dinv * r), and dinv[i] = 1.0f / a_ii
   std::vector<float> u(int col = 0) const;
@@ -1030,6 +1064,21 @@ private:
   int *stDone_() const { return reinterpret_cast<int *>(stIters_() + a_.nrhs); }
   int *stAllDone_() const { return stDone_() + a_.nrhs; }
   void upload_thresholds() const;
+  // refine_tol > 0: x64 and r64, n doubles each, and [r64 . r64 partials 256 | r . r partials 256 |
+  //  outer threshold f64 | last r64 . r64 f64 | outer steps i64 | outer_done i32 | pad]: a buffer
+  // of its own, so none of it shares a byte with dScal_ or dStop_
+  DeviceBuffer dX64_, dR64_, dRefine_;
+  double outerThresh_ = 0.0;
+  bool stepped_ = false; // a refinement step was taken since the last reset()
+  bool refining() const { return a_.refine_tol > 0; }
+  void check_refining(const char *what) const;
+  std::vector<double> down64(const DeviceBuffer &d) const;
+  double *rfP64_() const { return dRefine_.as<double>(); }
+  double *rfP32_() const { return rfP64_() + kern::kCgMaxPartials; }
+  double *rfThresh_() const { return rfP64_() + 2 * kern::kCgMaxPartials; }
+  double *rfRr64_() const { return rfThresh_() + 1; }
+  int64_t *rfSteps_() const { return reinterpret_cast<int64_t *>(rfThresh_() + 2); }
+  int *rfDone_() const { return reinterpret_cast<int *>(rfThresh_() + 3); }
 };
 
 /// Horizontal fusion (fused_ops.cpp): the halo's self moves `dirs` and the SpMV's local product

@@ -12,6 +12,10 @@ two launches: one matrix stream and one gather per entry serve every column. Wit
 that form stops each column on the device at r.r <= tol^2 b.b and freezes it; ``solve`` drives a
 prepared runtime until every column has stopped. ``precond="jacobi"`` runs that form preconditioned
 by diag(A), still in two launches; ``diag_scale`` poses the same problem in badly chosen units.
+``refine_tol`` > 0 wraps that f32 solve in f64 iterative refinement: the solution is kept in f64
+(``x64``), ``refine_step`` forms b - A x64 in f64 on the device and restarts the f32 recurrence on
+it, and ``solve`` repeats that until the f64 residual is below ``refine_tol`` ||b||. The step is
+not part of the searched schedule, batched refinement and an f64 matrix are not built.
 """
 from __future__ import annotations
 
@@ -49,6 +53,12 @@ class CgConfig:
     # d in 0..8: the same problem in badly chosen units, (S A S) y = S b with S = diag(2^e_i), e_i
     # uniform in [-d, d] from seed; exact in f32. scale() returns S's diagonal. 0: as generated / read
     diag_scale: int = 0
+    # > 0 (form="sr", nrhs=1, tol > 0, refine_tol < tol): f64 iterative refinement around the f32
+    # solve. tol becomes the inner solve's relative tolerance (it stops at r.r <= tol^2 rhat.rhat,
+    # rhat the f32 right-hand side it was restarted with); refine_step() adds x to x64, forms
+    # r64 = b - A x64 in f64 and restarts, until r64.r64 <= refine_tol^2 b.b. x64(), r64(),
+    # outer_steps(), refined(), inner_threshold() and residual64() report. 0: off
+    refine_tol: float = 0.0
     prefix: str = "cg_"
 
     def args(self, rank: int = 0, size: int = 1, device: int = -1) -> "_tz.CgArgs":
@@ -56,7 +66,7 @@ class CgConfig:
         a.m, a.bw, a.nnz, a.seed = self.m, self.bw, self.nnz, self.seed
         a.matrix, a.form, a.lanes, a.rhs, a.prefix = self.matrix, self.form, self.lanes, self.rhs, self.prefix
         a.nrhs, a.rhs_first, a.tol = self.nrhs, self.rhs_first, self.tol
-        a.precond, a.diag_scale = self.precond, self.diag_scale
+        a.precond, a.diag_scale, a.refine_tol = self.precond, self.diag_scale, self.refine_tol
         a.rank, a.size, a.device = rank, size, device
         return a
 
@@ -80,18 +90,32 @@ class CgSolve:
     launched: int      # iterations launched: at most max(iterations) + check_every, and max_iters
     residual: list     # per column: the true residual ||b - A x|| / ||b|| of the x it ended with
     #                    (formed on the host; empty with solve(..., residual=False))
+    # refine_tol > 0 only (the defaults otherwise):
+    outer_steps: int = 0        # restarts of the inner solve (refine_step calls that did not end it)
+    refined: bool = False       # a step found r64.r64 <= refine_tol^2 b.b
+    residual64: float = None    # ||b - A x64|| / ||b|| in f64 (None with residual=False)
 
 
-def solve(cg, rt, max_iters: int, check_every: int = 8, residual: bool = True) -> CgSolve:
+def solve(cg, rt, max_iters: int, check_every: int = 8, residual: bool = True, max_outer: int = 20) -> CgSolve:
     """Iterate a ``tol`` > 0 workload from its current state until every column has converged or
     ``max_iters`` iterations were launched. ``rt`` must have a schedule of this workload's graph
     prepared. The host looks at the device's flags only every ``check_every`` iterations; the
     iterations launched past a column's stop leave it untouched, so x, r, p and ``iterations`` do
-    not depend on ``check_every``."""
+    not depend on ``check_every``.
+
+    With ``refine_tol`` > 0, a look that finds the inner solve converged takes a ``refine_step()``;
+    the solve ends once that finds it refined, after ``max_iters`` inner iterations launched, or
+    once the inner solve has been restarted ``max_outer`` times. ``iterations`` then counts inner
+    iterations over the whole solve, ``converged`` and ``residual`` describe the last inner solve
+    (its x is a correction, 0 after a step), and x64 and the step counts do not depend on
+    ``check_every`` either."""
     if cg.args.tol <= 0:
         raise ValueError("solve needs a workload built with tol > 0")
     if max_iters < 0 or check_every < 1:
         raise ValueError("solve: max_iters >= 0 and check_every >= 1")
+    refine = cg.args.refine_tol > 0
+    if refine and max_outer < 1:
+        raise ValueError("solve: max_outer >= 1")
     cols = range(cg.args.nrhs)
     launched = 0
     while launched < max_iters:
@@ -100,6 +124,14 @@ def solve(cg, rt, max_iters: int, check_every: int = 8, residual: bool = True) -
         launched += n
         rt.device_sync()
         if all(cg.converged(j) for j in cols):
-            break
-    return CgSolve([cg.iterations(j) for j in cols], [cg.converged(j) for j in cols], launched,
-                   [cg.residual(j) for j in cols] if residual else [])
+            if not refine:
+                break
+            cg.refine_step()
+            if cg.refined() or cg.outer_steps() >= max_outer:
+                break
+    sol = CgSolve([cg.iterations(j) for j in cols], [cg.converged(j) for j in cols], launched,
+                  [cg.residual(j) for j in cols] if residual else [])
+    if refine:
+        sol.outer_steps, sol.refined = cg.outer_steps(), cg.refined()
+        sol.residual64 = cg.residual64() if residual else None
+    return sol
