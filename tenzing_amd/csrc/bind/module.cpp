@@ -1163,7 +1163,39 @@ PYBIND11_MODULE(_tz, m) {
       .def("add_to_graph", &DistSpmv::add_to_graph)
       .def("op_graph", [](DistSpmv &s) { return std::const_pointer_cast<Graph>(s.op_graph()); })
       .def("check", [](DistSpmv &s, uintptr_t st) { return s.check(P(st)); }, py::arg("stream") = 0)
-      .def("reset_y", [](DistSpmv &s, uintptr_t st) { s.reset_y(P(st)); }, py::arg("stream") = 0);
+      .def("reset_y", [](DistSpmv &s, uintptr_t st) { s.reset_y(P(st)); }, py::arg("stream") = 0)
+      .def("plan", [](const DistSpmv &s) {
+             auto arr = [](const auto &v) {
+               using T = typename std::decay_t<decltype(v)>::value_type;
+               return py::array_t<T>(py::ssize_t(v.size()), v.data());
+             };
+             auto csr = [&](const CsrHost &a) { return py::make_tuple(arr(a.rowPtr), arr(a.colInd), arr(a.val)); };
+             const DistSpmv::Plan p = s.plan();
+             py::dict d;
+             d["r0"] = p.r0;
+             d["r1"] = p.r1;
+             d["local"] = csr(p.local);
+             d["remote"] = csr(p.remote);
+             d["remote_cols"] = arr(p.remoteCols);
+             d["recv_count"] = arr(p.recvCount);
+             d["recv_off"] = arr(p.recvOff);
+             d["send_count"] = arr(p.sendCount);
+             d["send_off"] = arr(p.sendOff);
+             d["send_idx"] = arr(p.sendIdx);
+             return d;
+           }, "the host-side plan (no device needed): rows r0..r1, the local and remote blocks as "
+              "(rowPtr, colInd, val), the global column of each remote-x slot, and the receive and "
+              "send plans per rank")
+      .def("set_generation", &DistSpmv::set_generation, py::arg("gen"),
+           py::call_guard<py::gil_scoped_release>(),
+           "value generation 0..3 of x (0: the x of every ordinary run), uploaded in place; check() "
+           "then refers to it")
+      .def("generation", &DistSpmv::generation)
+      .def_static("x_gen", &DistSpmv::x_gen, py::arg("g"), py::arg("gen"))
+      .def("poison", &DistSpmv::poison, py::call_guard<py::gil_scoped_release>(),
+           "NaN-fill remote x, the send buffer, the partial products and y (y_r is zeroed instead "
+           "when the remote block is empty)")
+      .def("y", &DistSpmv::y, "the current y as a list of f32");
   m.def("move_spmv_op", [](std::shared_ptr<HaloExchange> h, std::vector<int> dirs, std::shared_ptr<DistSpmv> s,
                            std::string name, int lanes, bool intoY) {
     return make_move_spmv_op(h, std::move(dirs), s, std::move(name), lanes, intoY);

@@ -37,6 +37,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <limits>
 #include <random>
 
 namespace tz {
@@ -533,6 +534,8 @@ double ConjugateGradient::check(int k, int col) const {
   const std::vector<float> xd = this->x(col);
   double err = 0, scale = 0;
   for (size_t i = 0; i < n; ++i) {
+    // (std::max(err, NaN) is err: a NaN would pass as no error at all)
+    if (!std::isfinite(xd[i])) return std::numeric_limits<double>::infinity();
     err = std::max(err, std::abs(double(xd[i]) - x[i]));
     scale = std::max(scale, std::abs(x[i]));
   }

@@ -17,6 +17,7 @@
 #include <cctype>
 #include <cstring>
 #include <fstream>
+#include <limits>
 #include <random>
 #include <sstream>
 
@@ -227,6 +228,8 @@ static int owner_of(int64_t col, int64_t n, int size) {
 }
 
 static float x_value(int64_t g) { return float(int64_t((uint64_t(g) * 2654435761ull) % 2000ull) - 1000) / 1000.f; }
+
+float DistSpmv::x_gen(int64_t g, int gen) { return x_value(g + int64_t(gen) * 1000003); }
 
 namespace {
 
@@ -519,12 +522,9 @@ DistSpmv::DistSpmv(SpmvArgs a, Ctrl *ctrl) : a_(std::move(a)) {
   remote_.cols = int64_t(rc.size());
   local_.rowPtr.assign(size_t(nl + 1), 0);
   remote_.rowPtr.assign(size_t(nl + 1), 0);
-  yRef_.assign(size_t(nl), 0.0);
   for (int64_t i = 0; i < nl; ++i) {
-    double acc = 0;
     for (int32_t j = mine.rowPtr[size_t(i)]; j < mine.rowPtr[size_t(i + 1)]; ++j) {
       const int64_t c = mine.colInd[size_t(j)];
-      acc += double(mine.val[size_t(j)]) * double(x_value(c));
       if (c >= r0_ && c < r1_) {
         local_.colInd.push_back(int32_t(c - r0_));
         local_.val.push_back(mine.val[size_t(j)]);
@@ -534,7 +534,6 @@ DistSpmv::DistSpmv(SpmvArgs a, Ctrl *ctrl) : a_(std::move(a)) {
         remote_.val.push_back(mine.val[size_t(j)]);
       }
     }
-    yRef_[size_t(i)] = acc;
     local_.rowPtr[size_t(i + 1)] = int32_t(local_.colInd.size());
     remote_.rowPtr[size_t(i + 1)] = int32_t(remote_.colInd.size());
   }
@@ -553,8 +552,7 @@ DistSpmv::DistSpmv(SpmvArgs a, Ctrl *ctrl) : a_(std::move(a)) {
     for (int64_t c : needFrom[size_t(q)]) sendIdx_.push_back(int32_t(c - r0_));
     sendCount_[q] = int32_t(needFrom[size_t(q)].size());
   }
-  xLocal_.resize(size_t(nl));
-  for (int64_t i = 0; i < nl; ++i) xLocal_[size_t(i)] = x_value(r0_ + i);
+  fill_generation();
   TZ_CHECK(a_.transport == "auto" || a_.transport == "rccl" || a_.transport == "ipc",
            "SpMV transport must be auto, rccl or ipc (got " << a_.transport << ")");
   useRccl_ = a_.size > 1 && a_.transport != "ipc";
@@ -661,6 +659,49 @@ void DistSpmv::setup(Ctrl *ctrl) {
   TZ_HIP(hipDeviceSynchronize());
 }
 
+void DistSpmv::fill_generation() {
+  const size_t nl = size_t(r1_ - r0_);
+  xLocal_.resize(nl);
+  for (size_t i = 0; i < nl; ++i) xLocal_[i] = x_gen(r0_ + int64_t(i), gen_);
+  std::vector<double> xr(remoteCols_.size());
+  for (size_t k = 0; k < xr.size(); ++k) xr[k] = double(x_gen(remoteCols_[k], gen_));
+  yRef_.assign(nl, 0.0);
+  for (size_t i = 0; i < nl; ++i) {
+    double acc = 0;
+    for (int32_t j = local_.rowPtr[i]; j < local_.rowPtr[i + 1]; ++j)
+      acc += double(local_.val[size_t(j)]) * double(xLocal_[size_t(local_.colInd[size_t(j)])]);
+    for (int32_t j = remote_.rowPtr[i]; j < remote_.rowPtr[i + 1]; ++j)
+      acc += double(remote_.val[size_t(j)]) * xr[size_t(remote_.colInd[size_t(j)])];
+    yRef_[i] = acc;
+  }
+}
+
+void DistSpmv::set_generation(int gen) {
+  TZ_CHECK(gen >= 0 && gen < kGenerations, "SpMV generation must be 0.." << kGenerations - 1 << " (got " << gen << ")");
+  gen_ = gen;
+  fill_generation();
+  if (!ready()) return; // setup() uploads x_local
+  TZ_HIP(hipDeviceSynchronize());
+  if (!xLocal_.empty()) dX_.upload(xLocal_.data(), xLocal_.size() * 4);
+  TZ_HIP(hipDeviceSynchronize());
+}
+
+void DistSpmv::poison() {
+  TZ_CHECK(ready(), "spmv not set up");
+  TZ_HIP(hipDeviceSynchronize());
+  for (DeviceBuffer *d : {&dXr_, &dSend_, &dYl_, &dY_}) TZ_HIP(hipMemset(d->get(), 0xFF, d->bytes()));
+  TZ_HIP(hipMemset(dYr_.get(), remote_.nnz() == 0 ? 0 : 0xFF, dYr_.bytes()));
+  TZ_HIP(hipDeviceSynchronize());
+}
+
+std::vector<float> DistSpmv::y() const {
+  TZ_CHECK(ready(), "spmv not set up");
+  TZ_HIP(hipDeviceSynchronize());
+  std::vector<float> y(static_cast<size_t>(local_rows()));
+  if (!y.empty()) dY_.download(y.data(), y.size() * 4);
+  return y;
+}
+
 void DistSpmv::reset_y(void *stream) {
   // synchronous: schedules run on non-blocking streams that do not order after `stream`
   TZ_HIP(hipMemsetAsync(dY_.get(), 0, dY_.bytes(), static_cast<hipStream_t>(stream)));
@@ -672,8 +713,11 @@ double DistSpmv::check(void *stream) {
   std::vector<float> y(static_cast<size_t>(local_rows()));
   dY_.download(y.data(), y.size() * 4);
   double err = 0;
-  for (size_t i = 0; i < y.size(); ++i)
+  for (size_t i = 0; i < y.size(); ++i) {
+    // (std::max(err, NaN) is err: a NaN would pass as no error at all)
+    if (!std::isfinite(y[i])) return std::numeric_limits<double>::infinity();
     err = std::max(err, std::abs(double(y[i]) - yRef_[i]) / std::max(1.0, std::abs(yRef_[i])));
+  }
   return err;
 }
 

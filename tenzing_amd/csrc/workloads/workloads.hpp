@@ -774,9 +774,43 @@ public:
   void add_to_graph(Graph &g);
   std::shared_ptr<const Graph> op_graph(); // the compound op's inner graph
 
-  /// max |y - y_ref| / max(1,|y_ref|) over local rows after a run
+  /// max |y - y_ref| / max(1,|y_ref|) over local rows after a run, against the reference of the
+  /// current generation; +inf when any y entry is not finite
   double check(void *stream = nullptr);
   void reset_y(void *stream = nullptr);
+
+  // Hooks for tests that hold the workload to a reference of their own (none is used by the
+  // search, the benchmark or the tools, which stay at generation 0).
+  /// Value generations of x, 0..3. Generation 0 is the x every run has always used, x_value(g)
+  /// for global index g; generation gen > 0 is x_value(g + gen * 1000003). The hash has period
+  /// 2000 in g, so a generation shifts its residues cyclically by 1283, 566 or 1849 of 2000: never
+  /// by 0, hence every entry differs between any two generations, and all values stay in [-1, 1).
+  static constexpr int kGenerations = 4;
+  static float x_gen(int64_t g, int gen);
+  /// Switch to generation `gen`: the local x is rewritten in place in its device buffer (when set
+  /// up; no reallocation, so compiled hipGraphs and the library handles stay valid) and the
+  /// reference of check() is recomputed from the local and remote blocks. Synchronous; nothing
+  /// of this workload may be running.
+  void set_generation(int gen);
+  int generation() const { return gen_; }
+  /// Fill the remote-x buffer, the send buffer, both partial products and y with 0xFF bytes (f32
+  /// NaNs), so that whatever a schedule does not write again shows in y. With an empty remote
+  /// block y_r is zeroed instead: spmv_remote() relies on those zeros. Flags, credits and
+  /// counters are not touched. Synchronous; nothing of this workload may be running, on any rank
+  /// that puts into this one.
+  void poison();
+  /// the current y (synchronizes the device)
+  std::vector<float> y() const;
+  /// the host-side plan, as built by the constructor (no device needed)
+  struct Plan {
+    int64_t r0, r1;                          // my rows
+    const CsrHost &local, &remote;           // columns: local x index / remote-x slot
+    const std::vector<int64_t> &remoteCols;  // global column of each remote-x slot
+    const std::vector<int32_t> &recvCount, &recvOff, &sendCount, &sendOff, &sendIdx;
+  };
+  Plan plan() const {
+    return {r0_, r1_, local_, remote_, remoteCols_, recvCount_, recvOff_, sendCount_, sendOff_, sendIdx_};
+  }
 
   // op bodies
   void scatter(void *stream) const;
@@ -822,6 +856,9 @@ private:
   std::vector<int32_t> sendIdx_;             // local x index of each send entry
   std::vector<float> xLocal_;
   std::vector<double> yRef_;
+  int gen_ = 0;
+  /// x_local and y_ref of generation gen_ (y_ref in f64 from the local, then the remote block)
+  void fill_generation();
   int lanes_ = 8;
   DeviceBuffer dLocalRow_, dLocalCol_, dLocalVal_, dRemoteRow_, dRemoteCol_, dRemoteVal_;
   DeviceBuffer dX_, dXr_, dSendIdx_, dSend_, dYl_, dYr_, dY_;
@@ -989,7 +1026,8 @@ public:
   /// writes them (the bits of the plain and fused forms' rr slab), summed in the kernels' order
   double rr(int col = 0) const;
   /// max |x - x_ref| / max |x_ref| against k iterations of CG in f64 on the host (same guards);
-  /// with precond "jacobi" against k iterations of CG preconditioned by the same dinv
+  /// with precond "jacobi" against k iterations of CG preconditioned by the same dinv; +inf when
+  /// any x entry is not finite
   double check(int k, int col = 0) const;
   /// the true residual ||b - A x||_2 / ||b||_2 of the current x, in f64 on the host (0 for b = 0).
   /// The single-reduction form's r is a recurrence of its own, so rr() no longer is this quantity

@@ -143,8 +143,13 @@ def main():
         out["transport"] = sp.transport()
         out["rccl_capture"] = sp.rccl_capture_note()
         out["rccl_graph_ok"] = sp.rccl_graph_ok()
+        # the independent model of this rank's rows (tenzing_amd/utils/dist_spmv_ref.py)
+        from tenzing_amd.utils import dist_spmv_ref as ref
+
+        rows = ref.Rows(ref.default_band(m, ctrl.size), *ref.row_partition(m, ctrl.rank, ctrl.size))
         rt = tz.HipRuntime(device=dev, n_streams=3, watchdog_s=60.0)
         res = []
+        gen = 0
         for mode in (tz.ExecMode.Eager, tz.ExecMode.Graph):
             rt.set_mode(mode)
             rt.set_graph_unroll(3 if mode == tz.ExecMode.Graph else 1)
@@ -154,23 +159,34 @@ def main():
                     msg = tz.random_rollout(tz.State(g, tz.Platform(3)), seed).json(True)
                 seq = tz.OpIndex(g).sequence_from_json(ctrl.bcast(msg, 0).decode())
                 names = [o.name for o in seq.ops()]
-                sp.reset_y()
+                # a new x and NaNs in everything a schedule must write: nothing left over from an
+                # earlier run or the preflights can pass; on every rank before any put can land
+                gen = (gen + 1) % ref.GENERATIONS
+                sp.set_generation(gen)
+                sp.poison()
                 if halo is not None:
                     halo.init_grid()
+                rt.device_sync()
                 ctrl.barrier()
                 rt.prepare(seq)
                 rt.run(1)
                 rt.device_sync()
                 ctrl.barrier()
                 err1 = sp.check()
+                ratio1 = rows.ratio(sp.y(), gen)
                 bad = halo.check_grid() if halo is not None else 0
                 ctrl.barrier()
                 rt.run(5)  # y = A x is idempotent: repeated iterations keep it right
                 rt.device_sync()
                 ctrl.barrier()
                 res.append(dict(mode=str(mode), seed=seed, err1=err1, err2=sp.check(), bad=int(bad),
+                                ratio1=ratio1, ratio2=rows.ratio(sp.y(), gen),
                                 ipc=any(n.startswith(("i_", "spmv_i_")) for n in names),
                                 ipc_err=sp.ipc_errors()))
+        # the search below measures the x of every ordinary run
+        sp.set_generation(0)
+        rt.device_sync()
+        ctrl.barrier()
         bench = tz.EmpiricalBenchmarker(rt, ctrl)
         o = tz.MctsOpts()
         o.n_iters = 6
@@ -178,6 +194,84 @@ def main():
         rt.set_mode(tz.ExecMode.Eager)
         r = tz.mcts_explore(g, tz.Platform(3), bench, ctrl, o)
         out["mcts"] = len(r.sims)
+        out["runs"] = res
+    elif case == "spmv_ref":
+        # every rank's y against the numpy model of the distributed product (tenzing_amd/utils/
+        # dist_spmv_ref.py), row by row within the derived bound, with a new value generation of
+        # x before every comparison: data left over from an earlier run or a preflight fails
+        import numpy as np
+        from tenzing_amd.models import SpmvConfig, build_spmv
+        from tenzing_amd.utils import dist_spmv_ref as ref
+        from tenzing_amd.utils import spmv_ref
+
+        W, R = ctrl.size, ctrl.rank
+        m = int(os.environ.get("TZ_TEST_M", "4099"))
+        nnz = int(os.environ.get("TZ_TEST_NNZ", "0"))
+        matrix = os.environ.get("TZ_TEST_MATRIX", "")
+        rt = tz.HipRuntime(device=dev, n_streams=3, watchdog_s=60.0)
+        res = []
+        gen = 0
+        for bw in [int(b) for b in os.environ.get("TZ_TEST_BWS", "0").split(",")]:
+            if matrix:
+                # the arrays the test wrote to the file
+                c = spmv_ref.squared(spmv_ref.lengths_case(int(os.environ["TZ_TEST_LENGTHS_ROWS"])))
+                A = ref.as_csr((c.row_ptr, c.col_ind, c.val))
+                cfg = SpmvConfig(matrix=matrix, transport="ipc")
+            else:
+                A = ref.default_band(m, W, bw, nnz)
+                cfg = SpmvConfig(m=m, bw=bw, nnz=nnz, transport="ipc")
+            sp, g = build_spmv(cfg, ctrl, dev)
+            keep.append((sp, g))
+            rows = ref.Rows(A, *ref.row_partition(len(A[0]) - 1, R, W))
+            assert sp.local_rows() == rows.r1 - rows.r0
+            out["transport"] = sp.transport()
+
+            def step(next_gen, seq, runs):
+                sp.set_generation(next_gen)
+                if seq is not None:
+                    sp.poison()
+                rt.device_sync()
+                ctrl.barrier()  # every rank's x and poison are in place before any put can land
+                if seq is not None:
+                    rt.prepare(seq)
+                rt.run(runs)
+                rt.device_sync()
+                ctrl.barrier()
+                return rows.ratio(sp.y(), next_gen)
+
+            for mode in (tz.ExecMode.Eager, tz.ExecMode.Graph):
+                rt.set_mode(mode)
+                rt.set_graph_unroll(3 if mode == tz.ExecMode.Graph else 1)
+                draw = 0
+                for k in range(4):
+                    msg = ""
+                    if R == 0:
+                        # the first schedule takes the library's local product, whatever the draws
+                        for _ in range(400):
+                            cand = tz.random_rollout(tz.State(g, tz.Platform(3)), draw)
+                            draw += 1
+                            if k > 0 or any("rocsparse" in o.name for o in cand.ops()):
+                                break
+                        msg = cand.json(True)
+                    seq = tz.OpIndex(g).sequence_from_json(ctrl.bcast(msg, 0).decode())
+                    names = [o.name for o in seq.ops()]
+                    gen = (gen + 1) % ref.GENERATIONS
+                    r1 = step(gen, seq, 1)
+                    err1 = sp.check()
+                    gen = (gen + 1) % ref.GENERATIONS
+                    r2 = step(gen, None, 1)  # a transport delivering the last run's data fails here
+                    err2 = sp.check()
+                    ctrl.barrier()
+                    rt.run(5)
+                    rt.device_sync()
+                    ctrl.barrier()
+                    r3 = rows.ratio(sp.y(), gen)
+                    say(bw, str(mode), k, r1, r2, r3)
+                    res.append(dict(bw=bw, mode=str(mode), k=k, ratio1=r1, ratio2=r2, ratio3=r3,
+                                    err1=err1, err2=err2, err3=sp.check(), ipc_err=sp.ipc_errors(),
+                                    local_nnz=sp.local_nnz(), remote_nnz=sp.remote_nnz(),
+                                    library=any("rocsparse" in n for n in names),
+                                    ipc=any(n.startswith("i_") for n in names)))
         out["runs"] = res
     elif case == "comm_ops":
         # the user-level RCCL ops between real ranks (TZ_RCCL_LOOPBACK=1): every rank's result

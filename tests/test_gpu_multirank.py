@@ -404,13 +404,16 @@ def test_links_cli_three_ranks_loopback(gpu, tmp_path):
 def test_spmv_ipc_loopback(gpu, world, case):
     """distributed SpMV (and SpMV + halo in one graph, BASELINE config 5) on several ranks of
     one GPU: RCCL refuses the shared device, so the x halo goes through IPC puts; every rank's
-    y is checked against the host reference after every schedule"""
+    y is checked against the host reference and, row by row, against the numpy model of the
+    distributed product, after every schedule, each from a new x and NaN-filled buffers"""
     res = _launch(case, world)
     for r in res:
         assert r["size"] == world and r["transport"] == "ipc"
         assert r["mcts"] == (6 if r["rank"] == 0 else 0)
         for run in r["runs"]:
             assert run["err1"] < 1e-4 and run["err2"] < 1e-4, run
+            # every row within the derived bound of the independent model, from poisoned buffers
+            assert run["ratio1"] <= 1.0 and run["ratio2"] <= 1.0, run
             assert run["bad"] == 0 and run["ipc_err"] == 0 and run["ipc"], run
 
 
@@ -625,6 +628,7 @@ def test_spmv_rccl_across_ranks_loopback(gpu, fail_schedule):
         assert r["mcts"] == (6 if r["rank"] == 0 else 0)
         for run in r["runs"]:
             assert run["err1"] < 1e-4 and run["err2"] < 1e-4, run
+            assert run["ratio1"] <= 1.0 and run["ratio2"] <= 1.0, run
             assert not run["ipc"], run
 
 

@@ -295,22 +295,45 @@ def test_halo_rccl_self_exchange(tz, gpu):
             assert halo.check_grid() == 0
 
 
+class _SpmvModel:
+    """one rank's y against the numpy model of the distributed product (tenzing_amd/utils/
+    dist_spmv_ref.py), row by row within the derived bound. `fresh` replaces reset_y(): the next
+    value generation of x and NaNs in every buffer a schedule must write, so that nothing left
+    over from an earlier run can pass."""
+
+    def __init__(self, sp, A):
+        from tenzing_amd.utils import dist_spmv_ref as ref
+
+        self.sp, self.ref = sp, ref
+        self.rows = ref.Rows(A, 0, len(A[0]) - 1)
+
+    def fresh(self):
+        self.sp.set_generation((self.sp.generation() + 1) % self.ref.GENERATIONS)
+        self.sp.poison()
+
+    def ratio(self):
+        return self.rows.ratio(self.sp.y(), self.sp.generation())
+
+
 @pytest.mark.parametrize("form", ["split", "accum", "choice"])
 def test_spmv_workload_correct(tz, gpu, form):
     from tenzing_amd.models import SpmvConfig, build_spmv
+    from tenzing_amd.utils.dist_spmv_ref import default_band
 
     sp, g = build_spmv(SpmvConfig(m=20000, form=form), tz.SelfCtrl(), device=0)
+    model = _SpmvModel(sp, default_band(20000, 1))
     rt = tz.HipRuntime(device=0, n_streams=2)
     seqs = tz.get_all_sequences(g, tz.Platform(2), max_seqs=40)
     assert len(seqs) >= 4
     for m in (tz.ExecMode.Eager, tz.ExecMode.Graph):
         rt.set_mode(m)
         for seq in seqs[:10]:
-            sp.reset_y()
+            model.fresh()
             rt.prepare(seq)
             rt.run(1)
             rt.device_sync()
             assert sp.check() < 1e-4
+            assert model.ratio() <= 1.0, seq.desc()
 
 
 @pytest.mark.parametrize("form", ["split", "accum"])
@@ -318,8 +341,10 @@ def test_spmv_every_local_kernel_variant(tz, gpu, form):
     """each alternative of the local-product ChoiceOp (wave64 kernels and the rocSPARSE
     library variant) computes the right y, eagerly and captured into a hipGraph"""
     from tenzing_amd.models import SpmvConfig, build_spmv
+    from tenzing_amd.utils.dist_spmv_ref import default_band
 
     sp, g = build_spmv(SpmvConfig(m=30000, form=form), tz.SelfCtrl(), device=0)
+    model = _SpmvModel(sp, default_band(30000, 1))
     by_variant = {}
     for seed in range(400):
         seq = tz.random_rollout(tz.State(g, tz.Platform(2)), seed)
@@ -335,12 +360,13 @@ def test_spmv_every_local_kernel_variant(tz, gpu, form):
     for m in (tz.ExecMode.Eager, tz.ExecMode.Graph):
         rt.set_mode(m)
         for name, seq in sorted(by_variant.items()):
-            sp.reset_y()
+            model.fresh()
             rt.prepare(seq)
             assert rt.effective_mode == m, name
             rt.run(2)
             rt.device_sync()
             assert sp.check() < 1e-4, (name, m)
+            assert model.ratio() <= 1.0, (name, m)
 
 
 def test_mcts_halo_on_gpu(tz, gpu):
@@ -530,16 +556,22 @@ def test_spmv_workload_from_matrix_market_file(tz, gpu, tmp_path):
                  f"{n} {n} {len(lines)}\n" + "\n".join(lines) + "\n")
     sp, g = build_spmv(SpmvConfig(matrix=str(f)), tz.SelfCtrl(), device=0)
     assert sp.args.m == n
+    # the model's matrix: the file through the host reader (tests/test_matrix_market.py holds it
+    # to its format: mirrored entries, duplicates summed), not through the workload
+    rows, cols, rp, ci, v = tz._tz.read_matrix_market(str(f))
+    assert (rows, cols) == (n, n)
+    model = _SpmvModel(sp, (rp, ci, v))
     rt = tz.HipRuntime(device=0, n_streams=2)
     for m in (tz.ExecMode.Eager, tz.ExecMode.Graph):
         rt.set_mode(m)
         for seed in range(6):
             seq = tz.random_rollout(tz.State(g, tz.Platform(2)), seed)
-            sp.reset_y()
+            model.fresh()
             rt.prepare(seq)
             rt.run(1)
             rt.device_sync()
             assert sp.check() < 1e-4, seq.desc()
+            assert model.ratio() <= 1.0, seq.desc()
 
 
 def test_runtime_trace_timeline(tz, gpu):
@@ -742,17 +774,21 @@ def test_config5_one_launch_schedule_is_exact(tz, gpu, alt):
                           stream_for=lambda n: 1 if n.startswith("he_") else 0)
     names = [o.name for o in seq.ops() if isinstance(o, tz._tz.BoundGpuOp)]
     assert (names == [alt]) == alt.startswith("hs_onelaunch"), names
+    from tenzing_amd.utils.dist_spmv_ref import default_band
+
+    model = _SpmvModel(s, default_band(20_000, 1))
     for mode in (tz.ExecMode.Eager, tz.ExecMode.Graph):
         rt = tz.HipRuntime(device=0, n_streams=4, mode=mode, graph_unroll=3)
         for gen in (1, 2):
             h.init_grid(gen=gen)
-            s.reset_y()
+            model.fresh()
             rt.device_sync()
             rt.prepare(seq)
             rt.run(1)
             rt.device_sync()
             assert h.check_grid() == 0, (alt, mode, gen)
             assert s.check() < 1e-4, (alt, mode, gen)
+            assert model.ratio() <= 1.0, (alt, mode, gen)
         del rt
 
 
